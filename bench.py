@@ -2,6 +2,13 @@
 """Benchmark of the DSWx-HLS per-pixel hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--tiles T] [--total-tiles M] [--masks] [--chain] [--placement ...]
+                    [--dump-outputs DIR] [--full]
+
+A run without --full does what the headline needs and nothing else: bring-up, the resident batch generated and placed,
+W warm-up steps, K timed steps, the outputs of the last step written when --dump-outputs asks for them, one line.
+--full adds everything else the line can carry: the parity checks against the oracle, the `strong` sub-record of a
+plain N > 1 command, the per-kernel split of --chain, and the legs after the timed regions (host_path, realloc_spread,
+single_tile, product_run, cpu_baseline).
 
 One "step" = one pass of the fused classify kernel over the tiles a GPU owns: synthetic
 3660x3660 HLS.L30 tiles (6 int16 bands + Fmask; `--masks` adds LAND/SHAD/OCEAN), generated
@@ -17,7 +24,7 @@ The resident batch is allocated by the library (dswx_batch_create) and PLACED be
 sections 5 - 6): by default dswx_batch_place_slide times ~100 placements of the output planes inside a VMM-backed
 address range 48 GiB longer than they are and keeps the best; `roofline.frac_first_come_placement`,
 `roofline.frac_kept_placement_probe` and `roofline.realloc_spread` keep what unplaced allocations give in the same line.
-Every rank checks tiles of its own batch against the oracle after timing (`parity_check.ranks`).
+With --full every rank checks tiles of its own batch against the oracle after timing (`parity_check.ranks`).
 Tiles are independent: there is no data-path collective.  RCCL (torch.distributed 'nccl') carries
 only the barrier around the timed region and the MAX over ranks of the elapsed time.
 
@@ -96,17 +103,26 @@ def parse_args():
                     help='skip the end-to-end leg (dswx_classify_host on 4 tiles from page-locked and from pageable planes, '
                          'all ranks at once; after the timed region)')
     ap.add_argument('--no-strong', action='store_true',
-                    help='--gpus N > 1 without --tiles / --total-tiles measures the weak record AND BASELINE configs[3] '
+                    help='--gpus N > 1 --full without --tiles / --total-tiles measures the weak record AND BASELINE configs[3] '
                          '(4096 tiles over the ranks, the `strong` sub-record of the line); this keeps the weak record only')
     ap.add_argument('--also-strong', action='store_true',
                     help='measure the `strong` sub-record (BASELINE configs[3]) after the first record whatever N is: at N = 1 '
                          'the one rank walks all 4096 tiles in 512-tile chunks (the weak batch is freed first: the same '
                          'sequence an N > 1 rank goes through, at its real sizes)')
     ap.add_argument('--no-product-run', action='store_true',
-                    help='skip the product-run leg of the plain N = 1 command (one full GeoTIFF-in / COG-out product of a '
+                    help='skip the product-run leg of the plain N = 1 --full command (one full GeoTIFF-in / COG-out product of a '
                          '3660 x 3660 tile in a child process, after the timed regions)')
     ap.add_argument('--no-single-tile', action='store_true',
                     help='skip the configs[1] leg (profiling runs: keeps the kernel statistics to the batch launches)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: the parity checks against the oracle, the strong sub-record of a '
+                         'plain N > 1 command, the per-kernel split of --chain, and the legs after the timed regions '
+                         '(host_path, realloc_spread, single_tile, product_run, cpu_baseline; each --no-* option above still '
+                         'drops its leg).  Without it a run sets up, warms up, times the steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, '
+                         '< 64 MB): the per-tile counters of every resident tile, and every output layer at a fixed, seeded '
+                         'sample of pixels of a fixed, seeded sample of tiles (rank 0\'s batch of the first record)')
     ap.add_argument('--cpu-parallel-worker', type=int, default=0, help=argparse.SUPPRESS)
     # the two-record plain command at toy sizes (tests/test_gpu_multirank.py: two ranks share one device there)
     ap.add_argument('--plain-tiles', type=int, default=0, help=argparse.SUPPRESS)
@@ -381,6 +397,35 @@ def rank_parity(ctx, batch, params, rank, tile0, n_tiles, chunks, distinct):
     return rec
 
 
+DUMP_LAYERS = ('diag', 'wtr1', 'wtr2', 'wtr', 'bwtr', 'conf', 'cloud')
+DUMP_SEED = 20240611               # fixes which tiles and pixels --dump-outputs samples
+DUMP_TILES = 8                     # sampled tiles: the first, the last and up to six more
+DUMP_PIXELS = 1 << 17              # sampled pixels per tile (the same positions in every sampled tile)
+
+
+def dump_outputs(ctx, batch, out_dir, tile0, n_tiles, chain=False):
+    """--dump-outputs: what the last timed step left in the resident batch, as float32 / float64 .npy files.  `counters`
+    holds the [n_tiles][3] per-tile counters of every resident tile; every output layer (with --chain also the SHAD and
+    LAND planes the step computed) is sampled at the same DUMP_PIXELS pixel positions of the same sampled tiles, both
+    drawn from DUMP_SEED, so two builds given the same arguments write comparable arrays (< 40 MB in all)."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    n_px = batch.n_pixels
+    rest = np.arange(1, n_tiles - 1)
+    tiles = sorted({0, n_tiles - 1} | set(rng.choice(rest, size=min(DUMP_TILES - 2, rest.size), replace=False).tolist()))
+    pixels = np.sort(rng.choice(n_px, size=min(DUMP_PIXELS, n_px), replace=False))
+    ctx.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'counters': batch.read_counters().astype(np.float64),
+              'sample_tiles': np.asarray(tiles, dtype=np.float64) + tile0,
+              'sample_pixels': pixels.astype(np.float64)}
+    for name in DUMP_LAYERS + (('shad', 'land') if chain else ()):
+        arrays[name] = np.stack([batch.read_tile(name, t).reshape(-1)[pixels] for t in tiles]).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+    return {'dir': out_dir, 'files': len(arrays), 'MB': round(sum(a.nbytes for a in arrays.values()) / 1e6, 1)}
+
+
 CHAIN_SUN = dict(azimuth=141.0, elevation=35.0, min_slope_angle=-5.0, max_sun_local_inc_angle=40.0)
 CHAIN_FOREST = [111, 113, 115, 116, 121, 123, 125, 126]
 CHAIN_MARGIN = 50                  # DEM_MARGIN_IN_PIXELS (:58)
@@ -584,14 +629,15 @@ def rank_plan(case, rank, world):
 
 def cases_of(args, world):
     """The measured configurations of this command line.  The first is the top-level record of the line.  A plain
-    `bench.py --gpus N` (N > 1, neither --tiles nor --total-tiles nor --chain) -- what the driver runs for the scaling
-    curve -- measures BOTH: the weak record (256 tiles per GPU = configs[2] x N) and, as the line's `strong` sub-record,
+    `bench.py --gpus N --full` (N > 1, neither --tiles nor --total-tiles nor --chain) measures BOTH: the weak record
+    (256 tiles per GPU = configs[2] x N) and, as the line's `strong` sub-record,
     BASELINE configs[3]: 4096 tiles split over the ranks, walked in 512-tile chunks, every chunk classified once under a
     parity check (--distinct-chunks)."""
     first = argparse.Namespace(total_tiles=args.total_tiles, tiles=args.tiles, distinct_chunks=args.distinct_chunks,
                                key=None)
     cases = [first]
-    if (world > 1 and args.plain_command and not args.no_strong) or (args.also_strong and not args.total_tiles and not args.chain):
+    if (world > 1 and args.plain_command and args.full and not args.no_strong) or \
+            (args.also_strong and not args.total_tiles and not args.chain):
         cases.append(argparse.Namespace(total_tiles=args.strong_total, tiles=args.strong_chunk, distinct_chunks=True,
                                         key='strong'))
     return cases
@@ -770,7 +816,7 @@ def measure_case(args, case, env, case_index=0):
     my_tiles, tile0, n_tiles, chunks = rank_plan(case, rank, world)
     how = 'first' if env.share_device and args.placement != 'arena' else args.placement
     st = argparse.Namespace(batch=None, chain=None, placement={'how': how, 'probes': 0}, kernel_info=None,
-                            starts=[], stops=[], step_ms=[], chain_split=None)
+                            starts=[], stops=[], step_ms=[], chain_split=None, dump=None)
 
     def place():
         st.batch, st.placement = place_batch(ctx, params, n_tiles, tile0, args.masks, how, args.placement_trials,
@@ -811,13 +857,17 @@ def measure_case(args, case, env, case_index=0):
     closing_degraded = cp.barrier()          # True on EVERY rank if an RCCL barrier failed / hung on any (shard.ControlPlane.barrier)
     elapsed = time.perf_counter() - t0
     my_elapsed = elapsed
+    if args.dump_outputs and case_index == 0 and rank == 0:     # what the last timed step computed, before anything else runs
+        def dump():
+            st.dump = dump_outputs(ctx, st.batch, args.dump_outputs, tile0, n_tiles, chain=st.chain is not None)
+        guard.run('dump outputs', dump)
 
     def after():
         st.step_ms = [ctx.elapsed_ms(a, b) for a, b in zip(st.starts, st.stops)]
         for e in st.starts + st.stops:
             ctx.destroy_event(e)
         st.starts, st.stops = [], []
-        if st.chain and rank == 0:          # after the timed region: the three kernels of a step timed one by one
+        if st.chain and rank == 0 and args.full:    # after the timed region: the three kernels of a step timed one by one
             chain, batch = st.chain, st.batch
 
             def ms_of(fn, reps=10):
@@ -878,7 +928,7 @@ def measure_case(args, case, env, case_index=0):
     failed = [r for r in per_rank if 'error' in r]
 
     parity = None
-    if not args.no_parity:              # EVERY rank checks its own tiles; the records are gathered into the line
+    if args.full and not args.no_parity:    # EVERY rank checks its own tiles; the records are gathered into the line
         rec = None
         if guard.ok:                    # (the checker failing is reported, not fatal to the measurement)
             try:
@@ -948,6 +998,8 @@ def measure_case(args, case, env, case_index=0):
             'ranks': per_rank,
             'parity_check': parity,
         }
+        if st.dump:
+            out['dump_outputs'] = st.dump
         if failed:
             out['error'] = '; '.join(f"rank {r['rank']} failed in {r['phase']}: {r['error']}" for r in failed)[:1200]
             out['failed_ranks'] = [r['rank'] for r in failed]
@@ -1300,9 +1352,9 @@ def _main():
     if last_words:
         last_words.running = 'the legs after the timed regions'
 
-    # ---- legs after the timed regions (none of them is `value`)
+    # ---- legs after the timed regions (none of them is `value`; --full only)
     host_path = None
-    if not args.no_host_path and not args.chain and not failed_any:       # (every rank knows `failed_any`: gathered)
+    if args.full and not args.no_host_path and not args.chain and not failed_any:  # (every rank knows `failed_any`: gathered)
         # every rank takes part (all ranks at once, rates summed); a rank's failure is a record, not an exit
         host_path = host_path_leg(ctx, cp, env.params, check=not args.no_parity, rank=rank)
     # RCCL prints a version banner through C stdio, which is block-buffered when stdout is a pipe and would otherwise
@@ -1321,7 +1373,7 @@ def _main():
         out['config']['control_plane'] = cp.backend
         if host_path is not None:
             out['host_path'] = host_path
-        solo = world == 1 and not failed_any
+        solo = args.full and world == 1 and not failed_any
         if solo and args.realloc_repeats > 0 and not args.chain:
             try:
                 # the legs below allocate whole batches with hipMalloc: hand the library's pool (the chunks of the placed
@@ -1339,7 +1391,7 @@ def _main():
                 out['single_tile'] = {'error': f'{type(e).__name__}: {e}'[:300]}
         if solo and args.plain_command and not args.plain_tiles and not args.no_product_run:
             out['product_run'] = product_run_leg()
-        if world == 1 and not args.no_cpu_baseline and not failed_any:
+        if solo and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline_sample()
                 par = cpu_baseline_parallel()

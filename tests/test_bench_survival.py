@@ -200,7 +200,7 @@ def test_world_above_one_without_master_port_fails_at_once(tmp_path):
 # ------------------------------------------------------------------ (b) + (c): bench.py's own control flow, two ranks
 
 TOY = ['--gpus', '2', '--plain-tiles', '3', '--strong-total', '16', '--strong-chunk', '4', '--steps', '3', '--warmup', '1',
-       '--no-host-path']
+       '--no-host-path', '--full']
 
 
 def test_healthy_two_rank_line_has_both_records_the_fallback_notice_and_the_preflight():
@@ -215,6 +215,18 @@ def test_healthy_two_rank_line_has_both_records_the_fallback_notice_and_the_pref
     for r in pre['ranks']:
         assert r['hbm_free_GiB'] == 280.0 and r['control_plane_round_trip_ms'] > 0 and r['slide_slack_GiB'] == 48.0
     assert '[bench partial]' in res.stderr
+
+
+def test_plain_line_without_full_carries_the_headline_only():
+    """Without --full the plain command measures the weak record alone: no `strong` sub-record, no parity check, no legs
+    after the timed region; the headline fields are those of the full line."""
+    res = _torchrun(FAKE_RANK, *[a for a in TOY if a not in ('--full', '--no-host-path')])
+    assert res.returncode == 0, res.stderr[-3000:]
+    out = _line(res)
+    assert out['value'] > 0 and out['ms_per_step'] > 0 and out['steps'] == 3 and 'error' not in out
+    assert out['unit'] == 'Mpixels/s' and out['higher_is_better'] is True and out['dtype'] == 'int16+f64'
+    assert 'strong' not in out and out['parity_check'] is None and 'host_path' not in out
+    assert [r['rank'] for r in out['ranks']] == [0, 1] and out['preflight']['ok']
 
 
 @pytest.mark.parametrize('phase', ['place', 'warm-up', 'timed region'])
@@ -269,15 +281,15 @@ def test_a_rank_that_dies_hard_still_leaves_rank_zero_its_last_words(case_no):
 
 
 def test_preflight_alone_and_a_rank_short_of_hbm_shrinks_its_slack():
-    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight')
+    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight', '--full')
     assert res.returncode == 0, res.stderr[-3000:]
     pre = _line(res, '{"preflight"')['preflight']
     # the plain command: the largest resident chunk is the strong case's 512 tiles = 134.1 GiB + 48 GiB of slack
     assert pre['ok'] and [r['resident_chunk_GiB'] for r in pre['ranks']] == [134.14, 134.14]
-    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight', env={'FAKE_FREE_HBM_GIB': '160'})
+    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight', '--full', env={'FAKE_FREE_HBM_GIB': '160'})
     pre = _line(res, '{"preflight"')['preflight']
     assert pre['ok'] and all(r['slide_slack_GiB'] == 19.0 and '48 -> 19' in r['adjusted'] for r in pre['ranks'])
-    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight', env={'FAKE_FREE_HBM_GIB': '100'})
+    res = _torchrun(FAKE_RANK, '--gpus', '2', '--preflight', '--full', env={'FAKE_FREE_HBM_GIB': '100'})
     assert res.returncode != 0
     pre = _line(res, '{"preflight"')['preflight']
     assert not pre['ok'] and all('likely to fail' in r['warning'] for r in pre['ranks'])

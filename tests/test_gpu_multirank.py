@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(*argv, share_device=True, force_dist=False, extra_env=None, expect_rc=0):
+def _bench(*argv, share_device=True, force_dist=False, extra_env=None, expect_rc=0, full=True):
     env = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT', 'DSWX_BENCH_SHARE_DEVICE', 'DSWX_FORCE_DIST'):
         env.pop(k, None)
@@ -26,7 +26,9 @@ def _bench(*argv, share_device=True, force_dist=False, extra_env=None, expect_rc
     env.update(extra_env or {})
     # a child process (never exec from a process that touched the GPU); the parent bench process itself starts the
     # ranks with torch.distributed.run before it imports torch
-    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + list(argv), capture_output=True, text=True,
+    # --full: the parity records, the strong sub-record and the legs these tests check are not part of a plain run
+    argv = list(argv) + (['--full'] if full else [])
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + argv, capture_output=True, text=True,
                          timeout=1500, cwd=ROOT, env=env)
     assert (res.returncode == 0) == (expect_rc == 0), res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{"metric"')]
@@ -267,3 +269,38 @@ def test_a_rank_whose_allocation_fails_is_a_record_and_the_memory_comes_back():
     assert out['value'] is None and out['failed_ranks'] == [0, 1] and out['roofline'] is None
     assert all(r['phase'] == 'place' and 'DswxError' in r['error'] for r in out['ranks'])
     assert any('likely to fail' in r.get('warning', '') for r in out['preflight']['ranks'])
+
+
+def test_plain_run_dumps_what_its_last_step_computed(tmp_path):
+    """Without --full a run times its steps and prints the headline only; --dump-outputs DIR writes what the last timed
+    step left in the batch -- the counters of every tile and every layer at a seeded sample of pixels of a seeded sample of
+    tiles, float32 / float64 -- and those arrays are the C oracle's on the same synthetic tiles."""
+    import numpy as np
+    from oracle import c_oracle
+    from proteus_amd import _capi
+    from proteus_amd.synth import synth_tile
+    side, n_tiles = 1024, 5
+    out = _bench('--tiles', str(n_tiles), '--steps', '3', '--warmup', '1', '--tile-size', str(side),
+                 '--dump-outputs', str(tmp_path), share_device=False, full=False)
+    assert out['value'] > 0 and out['ms_per_step'] > 0 and out['steps'] == 3 and out['warmup'] == 1
+    assert out['roofline']['launches_timed'] == 3
+    assert out['parity_check'] is None
+    assert not {'host_path', 'single_tile', 'product_run', 'cpu_baseline', 'strong'} & set(out)
+    assert 'realloc_spread' not in out['roofline']
+    files = {f.name[:-4]: np.load(f) for f in tmp_path.glob('*.npy')}
+    assert set(files) == {'counters', 'sample_tiles', 'sample_pixels', 'diag', 'wtr1', 'wtr2', 'wtr', 'bwtr', 'conf', 'cloud'}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in tmp_path.glob('*.npy')) < 64 << 20
+    assert out['dump_outputs']['files'] == len(files)
+    tiles = files['sample_tiles'].astype(np.int64)
+    pixels = files['sample_pixels'].astype(np.int64)
+    assert tiles[0] == 0 and tiles[-1] == n_tiles - 1 and len(tiles) == n_tiles
+    assert len(pixels) == 1 << 17 and len(np.unique(pixels)) == len(pixels)
+    params = _capi.default_params()
+    for t in range(n_tiles):
+        s = synth_tile(t, side, side)
+        exp = c_oracle.classify(params, s['bands'], s['fmask'])
+        assert files['counters'][t].tolist() == exp['counters'].tolist(), t
+        i = tiles.tolist().index(t)
+        for key in ('diag', 'wtr1', 'wtr2', 'wtr', 'bwtr', 'conf', 'cloud'):
+            assert np.array_equal(files[key][i], exp[key].reshape(-1)[pixels].astype(np.float32)), (t, key)

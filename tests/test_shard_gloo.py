@@ -133,12 +133,12 @@ def test_bench_self_launch_weak_scaling_and_single_rank_plan():
 
 
 def test_plain_gpus_command_plans_the_weak_and_the_strong_record():
-    """`bench.py --gpus N` with nothing else -- what the driver runs for the scaling curve -- yields
+    """`bench.py --gpus N --full` with nothing else yields
     BOTH records in its one line: the weak one at the top level (256 tiles per GPU = configs[2] x N) and BASELINE
     configs[3] as the `strong` sub-record (4096 tiles split over the ranks, 512-tile resident chunks).  Naming a workload
-    (--tiles / --total-tiles / --masks / --chain) or --no-strong keeps the one record that was asked for."""
+    (--tiles / --total-tiles / --masks / --chain), --no-strong or leaving out --full keeps the one record that was asked for."""
     import json
-    res = _bench('--gpus', '2', '--plan-only')
+    res = _bench('--gpus', '2', '--plan-only', '--full')
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
     assert out['scaling'] == 'weak' and out['tiles_per_step_all_ranks'] == 512
@@ -147,7 +147,7 @@ def test_plain_gpus_command_plans_the_weak_and_the_strong_record():
     assert st['scaling'] == 'strong' and st['tiles_per_step_all_ranks'] == 4096 and st['n_gpus'] == 2
     assert [(r['first_tile'], r['tiles'], r['launches']) for r in st['ranks']] == \
         [(0, 2048, [512] * 4), (2048, 2048, [512] * 4)]
-    for extra in (['--no-strong'], ['--tiles', '8'], ['--masks']):
+    for extra in ([], ['--full', '--no-strong'], ['--full', '--tiles', '8'], ['--full', '--masks']):
         res = _bench('--gpus', '2', '--plan-only', *extra)
         out = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
         assert 'strong' not in out and out['scaling'] == 'weak', extra
