@@ -321,7 +321,27 @@ TILE_CASES = [
     # disabled for that plane), mixed with ordinary ones, with a Fmask fill of NaN
     dict(name='t64_fills_zero_max', tile=25, H=64, W=64, land=1, ocean=1, fills='zero_max'),
     dict(name='t72x40_fills_nan', tile=26, H=72, W=40, shad=1, fills='nan'),
+    # the whole byte range of the mask planes (_mask_domain): SHAD masks where it is 0 only (:1333-1340), OCEAN is ocean
+    # where it is 0 (:5245) but n_not_ocean sums the byte values (:5105), LAND is a 0..255 code
+    dict(name='t128_wide_ocean_0_255', tile=27, H=128, W=128, land=1, shad=1, ocean=1, domains=dict(ocean='0/255')),
+    dict(name='t129x97_wide_shad_ocean', tile=28, H=129, W=97, shad=1, ocean=1,
+         domains=dict(shad='0..255', ocean='0..255')),
+    dict(name='t128_wide_all_masks', tile=29, H=128, W=128, land=1, shad=1, ocean=1,
+         domains=dict(land='0..255', shad='0..255', ocean='0..255')),
+    dict(name='t160x112_cover_wide', tile=30, H=160, W=112, land=1, shad=1, ocean=1, mode='cover',
+         domains=dict(land='0..255', shad='0..255', ocean='0/255')),
 ]
+
+
+def _mask_domain(plane, domain, rng):
+    """A LAND / SHAD / OCEAN plane of synth_tile in another byte domain: the recipe's zeros stay zero, the other pixels
+    become 255 ('0/255') or uniform over 0..255 ('0..255'; LAND has no zeros, so it is uniform everywhere)."""
+    keep = plane != 0
+    if domain == '0/255':
+        return np.where(keep, 255, 0).astype(np.uint8)
+    if domain == '0..255':
+        return np.where(keep, rng.integers(0, 256, size=plane.shape), 0).astype(np.uint8)
+    raise ValueError(domain)
 
 
 def _corridor_tile(H, W):
@@ -434,6 +454,15 @@ def gen_tiles(ref):
         land = s['land'] if case.get('land') else None
         shad = s['shad'].astype(bool) if case.get('shad') else None
         ocean = s['ocean'] if case.get('ocean') else None
+        if case.get('domains'):
+            drng = np.random.default_rng(3000 + case['tile'])     # (its own stream, as the fills above)
+            dom = case['domains']
+            if land is not None and 'land' in dom:
+                land = _mask_domain(s['land'], dom['land'], drng)
+            if shad is not None and 'shad' in dom:
+                shad = _mask_domain(s['shad'], dom['shad'], drng)       # the bytes themselves, not a bool plane
+            if ocean is not None and 'ocean' in dom:
+                ocean = _mask_domain(s['ocean'], dom['ocean'], drng)
         mode = case.get('mode', 'mask')
         thr_tag = case.get('thr', 'default')
         thr = make_thresholds(ref, **ALT_THRESHOLDS[thr_tag])

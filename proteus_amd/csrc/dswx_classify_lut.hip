@@ -145,13 +145,19 @@ __global__ __launch_bounds__(256, WPS) void dswx_classify_lut(const KArgs a, con
         for (int sh = 32; sh > 0; sh >>= 1) { c0 += __shfl_xor(c0, sh); c2 += __shfl_xor(c2, sh); }
         if (a.fold_acc) {
             // Counters folded into this kernel (launches of a few tiles): two levels of last-block-done, ONE atomic per block,
-            // no fence.  The blocks of a tile form groups of 2^a.fold_group_log2 blocks (<= 2^17 pixels); every group and every
+            // no fence.  The blocks of a tile form groups of 2^a.fold_group_log2 blocks (<= 2^16 pixels); every group and every
             // tile has an accumulator on a 128-byte line of its own, so that the groups' atomics spread over the memory
             // channels (one accumulator per tile serialised 6,541 same-address atomics and cost a 3660 x 3660 launch 35 us,
             // and a __threadfence per block -- an L2 write-back on this part -- cost six times the kernel: both measured
-            // in round 5).  A block adds  valid | cloud_and_valid << 19 | not_ocean << 38 | ONE TICKET << 57  to its group:
+            // in round 5).  A block adds  valid | cloud_and_valid << 17 | not_ocean << 34 | ONE TICKET << 58  to its group:
             // the value the atomic returns tells the block whether it drew the group's last ticket, and if so it also holds
-            // the group's complete sums.  That block forwards them to the tile: n_not_ocean first (its own word; the atomic
+            // the group's complete sums.  not_ocean is the SUM OF THE OCEAN BYTES (the reference's np.sum(ocean_mask), :5105),
+            // up to 255 per pixel: a group of at most 2^16 pixels needs 17 + 17 + 24 bits for its sums and 6 for its ticket
+            // (<= 32 blocks), exactly 64.  (Groups of 2^17 pixels with 19-bit fields, before, let a 0/255 plane's ocean sum
+            // carry into the ticket: the last-block test misfired, counters[tile] was never written and the accumulators
+            // were left dirty for the next launch.  Halving the groups keeps one atomic per block, where a separate ocean
+            // word per group would add a second, waited-for one; the price is twice as many group-to-tile forwards, ~200
+            // more per 3660 x 3660 tile.)  That block forwards them to the tile: n_not_ocean first (its own word; the atomic
             // RETURNS, so it has been performed), then valid | cloud << 24 | one ticket << 48 -- made data-dependent on that
             // return -- and whoever draws the tile's last ticket reads the n_not_ocean word complete, writes counters[tile]
             // and leaves every accumulator zero for the next launch.  (The host folds only tiles < 2^24 pixels.)
@@ -168,13 +174,13 @@ __global__ __launch_bounds__(256, WPS) void dswx_classify_lut(const KArgs a, con
                 const long long in_group = min(gb, a.blocks_per_tile - (g << sh));
                 unsigned long long* tacc = a.fold_acc + tile * (G + 1) * 16;        // [tile][1 + G] lines of 16 u64
                 unsigned long long* gacc = tacc + (1 + g) * 16;
-                const unsigned long long add = v | cl << 19 | oc << 38 | 1ull << 57;
+                const unsigned long long add = v | cl << 17 | oc << 34 | 1ull << 58;
                 const unsigned long long now = atomicAdd(gacc, add) + add;
-                if ((long long)(now >> 57) == in_group) {               // the group's last block: `now` holds the group's sums
+                if ((long long)(now >> 58) == in_group) {               // the group's last block: `now` holds the group's sums
                     atomicExch(gacc, 0ull);
-                    unsigned long long tadd = (now & 0x7ffffull) | ((now >> 19) & 0x7ffffull) << 24 | 1ull << 48;
+                    unsigned long long tadd = (now & 0x1ffffull) | ((now >> 17) & 0x1ffffull) << 24 | 1ull << 48;
                     if (has_o) {
-                        unsigned long long seen = atomicAdd(tacc + 1, (now >> 38) & 0x7ffffull);
+                        unsigned long long seen = atomicAdd(tacc + 1, (now >> 34) & 0xffffffull);
                         asm volatile("" : "+v"(seen));                  // (opaque: the ticket below waits for this return)
                         tadd += seen >> 63;                             // always 0
                     }
@@ -196,9 +202,12 @@ __global__ __launch_bounds__(256, WPS) void dswx_classify_lut(const KArgs a, con
 }
 
 // `lead_max`: the largest per-tile lead-in of the launch (0 when every tile starts 256-byte aligned, else 31 groups)
-// log2 of the blocks per group of the folded counters: at most 2^17 pixels per group (19-bit fields of the group accumulator)
-static_assert(LUT_EXTRAS_CHUNKS == 4, "dswx_lut_fold_group_log2 assumes 64 / 4 = 16 blocks of 8192 pixels");
-int dswx_lut_fold_group_log2(bool extras) { return extras ? 4 : 6; }
+// log2 of the blocks per group of the folded counters: at most 2^16 pixels per group, so that the group accumulator's
+// fields hold their sums (valid and cloud <= 2^16: 17 bits; not_ocean <= 255 * 2^16 < 2^24: 24 bits; ticket <= 32: 6 bits)
+static_assert(LUT_EXTRAS_CHUNKS == 4, "dswx_lut_fold_group_log2 assumes 32 / 4 = 8 blocks of 8192 pixels");
+static_assert(17 + 17 + 24 + 6 == 64 && (255ull << 16) < (1ull << 24),
+              "group accumulator: valid 17 | cloud 17 | not_ocean 24 | ticket 6 bits for groups of 2^16 pixels");
+int dswx_lut_fold_group_log2(bool extras) { return extras ? 3 : 5; }
 
 void dswx_lut_geometry(const dswx_ctx* ctx, long long groups, bool extras, int lead_max, int* threads, long long* gx) {
     (void)ctx;

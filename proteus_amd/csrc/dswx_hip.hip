@@ -684,7 +684,7 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
             const bool fold = variant && b.counters && nt <= DSWX_FOLD_MAX_TILES && n_pixels < (1LL << 24) && gx < 65536 &&
                               ctx->tune_fold != 0;
             if (fold) {
-                // [tile][1 + groups of 64 blocks] accumulators, one 128-byte line each: zeroed when (re)allocated or after a
+                // [tile][1 + groups of 2^gl blocks] accumulators, one 128-byte line each: zeroed when (re)allocated or after a
                 // failed launch, left zero by every launch that completes
                 const int gl = dswx_lut_fold_group_log2(!plain_outputs);
                 const size_t need = (size_t)nt * (size_t)(1 + ((gx + (1LL << gl) - 1) >> gl)) * 128;

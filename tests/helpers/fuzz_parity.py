@@ -21,6 +21,17 @@ from oracle import c_oracle                         # noqa: E402  (checker)
 from proteus_amd import _capi                       # noqa: E402
 from proteus_amd.synth import synth_tile            # noqa: E402
 from tests.test_gpu_parity import _random_case, ALL_LAYERS   # noqa: E402
+from tests.test_gpu_mask_domain import with_mask_domains      # noqa: E402
+
+
+def wide_masks(s, seed, it):
+    """The mask planes of a synthetic tile in a random byte domain each (recipe {0, 1} / codes, {0, 255}, 0..255, ...):
+    the reference reads the whole byte (SHAD and OCEAN mask at 0, n_not_ocean sums the OCEAN bytes).  Its own generator,
+    so that the other draws of an iteration stay what they were."""
+    mrng = np.random.default_rng([seed, it, 255])
+    dom = dict(ocean=str(mrng.choice(['recipe', 'recipe', '0/255', '0..255', '0..4', 'all 255', 'all 0'])),
+               shad=str(mrng.choice(['recipe', '0/255', '0..255'])), land=str(mrng.choice(['recipe', '0..255'])))
+    return with_mask_domains(s, seed=int(mrng.integers(1 << 30)), **dom)
 
 
 def device_batch_soak(ctx, rng, a, kernels):
@@ -41,6 +52,11 @@ def device_batch_soak(ctx, rng, a, kernels):
         batch = _capi.DeviceBatch(ctx, n_tiles, h, w, masks=masks, extra_layers=extra, tile_align=align,
                                   separate_outputs=form == 'separate', sliding_outputs=form == 'sliding')
         batch.synth(777 + it, tile0=it)
+        if masks:                                       # the mask planes in wide byte domains (read back for the oracle below)
+            for t in range(n_tiles):
+                st = wide_masks({m: batch.read_tile(m, t) for m in ('land', 'shad', 'ocean')}, a.seed, it * 64 + t)
+                for m in ('land', 'shad', 'ocean'):
+                    batch.write_tile(m, t, st[m])
         mode = str(rng.choice(['mask', 'ignore', 'cover']))
         p = _capi.make_params(
             cs['thr'], clip_negative_reflectance=cs['clip'], mask_adjacent_to_cloud_mode=mode,
@@ -112,7 +128,7 @@ def odd_planes_soak(ctx, rng, a, kernels):
                               apply_aerosol_class_remapping=cs['aerosol'], aerosol_fmask_values=cs['lists'],
                               collapse_wtr_classes=cs['collapse'], aerosol_max_nir=None if mode == 'cover' else cs['aer_nir'],
                               offset_and_scale=scaled)
-        tiles = [synth_tile(9000 + 7 * it + t, h, w, with_masks=True) for t in range(n)]
+        tiles = [wide_masks(synth_tile(9000 + 7 * it + t, h, w, with_masks=True), a.seed, 100000 + 8 * it + t) for t in range(n)]
         in_names = list(_capi.BAND_NAMES) + ['fmask'] + (['land', 'shad', 'ocean'] if masks else [])
         out_names = ['diag', 'wtr1', 'wtr2', 'wtr', 'bwtr', 'conf', 'cloud'] + (['wtr1_aerosol'] if rng.integers(2) else [])
         sizes = {k: n * stride * (2 if (k in _capi.BAND_NAMES or k == 'diag') else 1) for k in in_names + out_names}
@@ -220,7 +236,7 @@ def main():
         h, w = int(rng.integers(1, 200)), int(rng.integers(1, 260))
         if kind == 3:
             h, w = int(rng.integers(200, 700)), 8 * int(rng.integers(30, 120))
-        s = synth_tile(5000 + it, h, w, with_masks=True)
+        s = wide_masks(synth_tile(5000 + it, h, w, with_masks=True), a.seed, it)
         bands = [b.copy() for b in s['bands']]
         fmask = s['fmask'].copy()
         if kind == 1:          # uniform int16 noise incl. the extremes, random Fmask bytes

@@ -54,7 +54,13 @@ def one_case(case, root):
     if rng.random() < 0.5:
         kw['shadow_layer'], okw['shadow'] = s['shad'].astype(bool), s['shad']
     if rng.random() < 0.4:
-        kw['ocean_mask'], kw['apply_ocean_masking'], okw['ocean_mask'] = s['ocean'], True, s['ocean']
+        ocean = s['ocean']
+        # half of those: a 0/255 byte mask (classification reads zero / non-zero, n_not_ocean sums the bytes); its own
+        # generator, so that the other draws of a case stay what they were
+        if np.random.default_rng((1000 + case, 255)).random() < 0.5:
+            ocean = (s['ocean'] * 255).astype(np.uint8)
+            desc['ocean_255'] = True
+        kw['ocean_mask'], kw['apply_ocean_masking'], okw['ocean_mask'] = ocean, True, ocean
     mode = str(rng.choice(['mask', 'ignore', 'cover']))
     kw['mask_adjacent_to_cloud_mode'] = okw['mask_adjacent_to_cloud_mode'] = mode
     scaled = rng.random() < 0.25
@@ -88,9 +94,12 @@ def one_case(case, root):
     for layer, path in outs.items():
         if layer in ('rgb', 'irgb', 'browse'):
             continue
-        arr, _ = geotiff.read_geotiff(path)
+        arr, info = geotiff.read_geotiff(path)
         if not np.array_equal(arr, exp[layer]):
             raise Mismatch(f'{desc}: layer {layer}: {int(np.count_nonzero(arr != exp[layer]))} pixels differ')
+        for key in ('SPATIAL_COVERAGE', 'SPATIAL_COVERAGE_EXCLUDING_MASKED_OCEAN', 'CLOUD_COVERAGE'):
+            if key in info.metadata and info.metadata[key] != str(exp['counters'][key]):
+                raise Mismatch(f'{desc}: layer {layer}: {key} {info.metadata[key]} != {exp["counters"][key]}')
         if geotiff.validate_cog(path):
             raise Mismatch(f'{desc}: layer {layer}: {geotiff.validate_cog(path)}')
         if arr.shape != (1, 1):
@@ -141,7 +150,7 @@ def main():
     logging.getLogger('dswx_hls').setLevel(logging.ERROR)
     D.get_context(0)
     t0 = time.perf_counter()
-    seen = {'mode': {}, 'outputs': {}, 'scaled': 0, 'multiband': 0, 'with_nodata_rows': 0}
+    seen = {'mode': {}, 'outputs': {}, 'scaled': 0, 'multiband': 0, 'with_nodata_rows': 0, 'ocean_255': 0}
     with tempfile.TemporaryDirectory() as root:
         try:
             with ThreadPoolExecutor(a.threads) as ex:
@@ -156,6 +165,7 @@ def main():
         seen['scaled'] += desc['scaled']
         seen['multiband'] += desc['multiband']
         seen['with_nodata_rows'] += desc['fill_rows'] > 0
+        seen['ocean_255'] += desc.get('ocean_255', False)
     print(json.dumps({'ok': True, 'cases': a.cases, 'threads': a.threads, 'seed': a.seed, 'files_checked': sum(n for n, _ in results),
                       'seen': seen, 'seconds': round(time.perf_counter() - t0, 1)}))
     return 0

@@ -43,6 +43,34 @@ def test_tile_chain_c(name):
         check_case(res, c, collapse, name)
 
 
+@pytest.mark.parametrize('shape', [(1, 1), (3, 5), (37, 53), (128, 128), (301, 263)])
+def test_c_and_numpy_oracles_on_wide_mask_bytes(shape):
+    """The two oracles agree on every layer and counter when LAND / SHAD / OCEAN take their whole byte range ({0, 255},
+    0..255, all 255, all 0, 0..4): SHAD masks at 0 only, OCEAN masks at 0 and n_not_ocean sums the bytes."""
+    from oracle import dswx_oracle as o
+    from tests.test_gpu_mask_domain import DOMAINS, tile_in
+    h, w = shape
+    wide = 0
+    for dom in range(len(DOMAINS)):
+        s = tile_in(dom, 40 + h, h, w)
+        wide += int(s['ocean'].max() > 1) + int(s['shad'].max() > 1)
+        for mode in ('mask', 'ignore'):
+            for collapse in (True, False):
+                p = _capi.make_params(mask_adjacent_to_cloud_mode=mode, collapse_wtr_classes=collapse)
+                got = c_oracle.classify(p, s['bands'], s['fmask'], land=s['land'], shad=s['shad'], ocean=s['ocean'])
+                with np.errstate(all='ignore'):
+                    exp = o.classify_tile(s['bands'], s['fmask'], landcover=s['land'], shadow=s['shad'],
+                                          ocean_mask=s['ocean'], mask_adjacent_to_cloud_mode=mode, collapse=collapse)
+                for layer, key in NAME.items():
+                    assert np.array_equal(got[key], exp[layer]), (shape, dom, mode, collapse, layer)
+                c = exp['counters']
+                assert got['counters'].tolist() == [c['n_valid'], c['n_cloud_and_valid'], c['n_not_ocean']], \
+                    (shape, dom, mode)
+                assert c['n_not_ocean'] == int(s['ocean'].sum(dtype=np.int64))
+    if h * w > 1:
+        assert wide >= 5             # the domains are really wide here
+
+
 def binary_repr(d):
     return sum(((d >> i) & 1) * 10 ** i for i in range(5)).astype(np.uint16)
 

@@ -240,6 +240,39 @@ def test_api_with_masks_and_multiband(tmp_path):
         assert info.metadata['MASK_ADJACENT_TO_CLOUD_MODE'] == 'cover'
 
 
+def test_ocean_mask_geotiff_of_0_and_255(tmp_path):
+    """generate_dswx_layers with an OCEAN GeoTIFF holding 0 / 255 (a common byte mask) against the same mask as 0 / 1.
+    Classification reads zero vs non-zero, so every layer of the product is byte-identical; the coverage counters follow
+    the reference, whose n_not_ocean = np.sum(ocean_mask) (:5105) sums the byte values: SPATIAL_COVERAGE_EXCLUDING_MASKED_
+    OCEAN is the oracle's for the 0 / 255 plane (the reference's quirk, kept on purpose)."""
+    rcfile, files, masks, s = synth_hls.make(str(tmp_path), size=300, tile=17, masks=True)
+    ocean01, oinfo = geotiff.read_geotiff(masks['ocean'])
+    assert set(np.unique(ocean01).tolist()) == {0, 1}
+    path255 = str(tmp_path / 'ocean_255.tif')
+    geo = geotiff.geo_tags_from_geotransform(oinfo.geotransform, epsg=32615)        # the grid of make_synthetic_hls
+    geotiff.write_geotiff(path255, (ocean01 * 255).astype(np.uint8), geo_tags=geo)
+    stacks, mds = {}, {}
+    for tag, ocean in (('01', masks['ocean']), ('255', path255)):
+        out = str(tmp_path / f'product_{tag}.tif')
+        assert D.generate_dswx_layers(files, out, apply_ocean_masking=True, mask_adjacent_to_cloud_mode='mask',
+                                      landcover_mask=masks['land'], shadow_layer=s['shad'], ocean_mask=ocean,
+                                      output_confidence_layer=str(tmp_path / f'conf_{tag}.tif'),
+                                      output_interpreted_band=str(tmp_path / f'wtr_{tag}.tif')) is True
+        stacks[tag], _ = geotiff.read_geotiff(out)
+        conf, _ = geotiff.read_geotiff(str(tmp_path / f'conf_{tag}.tif'))
+        wtr, info = geotiff.read_geotiff(str(tmp_path / f'wtr_{tag}.tif'))
+        stacks[tag] = (stacks[tag], conf, wtr)
+        mds[tag] = info.metadata
+    for a, b in zip(stacks['01'], stacks['255']):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
+    for tag, plane in (('01', ocean01), ('255', (ocean01 * 255).astype(np.uint8))):
+        c = o.classify_tile(s['bands'], s['fmask'], landcover=s['land'], shadow=s['shad'], ocean_mask=plane)['counters']
+        assert c['n_not_ocean'] == int(plane.sum(dtype=np.int64))
+        for key in ('SPATIAL_COVERAGE', 'CLOUD_COVERAGE', 'SPATIAL_COVERAGE_EXCLUDING_MASKED_OCEAN'):
+            assert mds[tag][key] == str(c[key]), (tag, key)
+    assert mds['01']['SPATIAL_COVERAGE_EXCLUDING_MASKED_OCEAN'] != mds['255']['SPATIAL_COVERAGE_EXCLUDING_MASKED_OCEAN']
+
+
 def test_offset_and_scale_inputs_flag(tmp_path):
     """flag_offset_and_scale_inputs (CLI --offset-and-scale-inputs, reference :2300-2302): the chain on float32
     reflectances scaled with the bands' own scale_factor / add_offset metadata (0.0001 / 0 in the synthetic files).
