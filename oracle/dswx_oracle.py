@@ -456,8 +456,9 @@ def decimate_by_summation(image, size_y, size_x):
 
 
 def landcover_mask_from_warped(worldcover_up3, copernicus, forest_classes, mask_type='standard',
-                               year=2000):
-    water = decimate_by_summation(np.isin(worldcover_up3, [80, 90, 95]).astype(np.uint8), 3, 3)
+                               year=2000, thresholds=None):
+    """thresholds: (tree, low, high, water), any integers, in place of LANDCOVER_THRESHOLDS[mask_type]."""
+    water =decimate_by_summation(np.isin(worldcover_up3, [80, 90, 95]).astype(np.uint8), 3, 3)
     urban = decimate_by_summation((worldcover_up3 == 50).astype(np.uint8), 3, 3)
     tree = decimate_by_summation((worldcover_up3 == 10).astype(np.uint8), 3, 3)
     forest = np.zeros_like(tree, dtype=np.uint8)
@@ -466,10 +467,12 @@ def landcover_mask_from_warped(worldcover_up3, copernicus, forest_classes, mask_
             forest |= (copernicus == c)
     tree = np.where(forest, tree, 0)
     land = np.full(water.shape, FILL_U8, dtype=np.uint8)
-    thr = LANDCOVER_THRESHOLDS[mask_type.lower()]
+    thr = LANDCOVER_THRESHOLDS[mask_type.lower()] if thresholds is None else [int(t) for t in thresholds]
     off = year - 2000
+    # the two developed classes are stored through the uint8 array: under the reference's pinned numpy 1.23.5 a class
+    # outside 0..255 wraps modulo 256 (numpy 2 raises OverflowError instead); the kernel's land_args does the same wrap
     land[tree >= thr[0]] = LAND_EVERGREEN
-    land[urban >= thr[1]] = LAND_LOW_DEV0 + off
-    land[urban >= thr[2]] = LAND_HIGH_DEV0 + off
+    land[urban >= thr[1]] = (LAND_LOW_DEV0 + off) & 0xff
+    land[urban >= thr[2]] = (LAND_HIGH_DEV0 + off) & 0xff
     land[water >= thr[3]] = LAND_WATER
     return land

@@ -599,7 +599,18 @@ def gen_browse(ref):
 LAND_CASES = [dict(name='l_standard', tile=0, H=90, W=120, year=2021, kind='standard'),
               dict(name='l_water_heavy', tile=1, H=64, W=64, year=2020, kind='water heavy'),
               dict(name='l_no_forest', tile=2, H=50, W=70, year=2000, kind='standard', forest=[]),
-              dict(name='l_odd', tile=3, H=33, W=41, year=2099, kind='standard')]
+              dict(name='l_odd', tile=3, H=33, W=41, year=2099, kind='standard'),
+              # full byte range (oracle/land_inputs.py, seeded by `seed`): WorldCover 0..255 mixed densely with the five
+              # codes and their +-1 neighbours, CGLS 0..255; edge forest lists; thresholds the reference never ships
+              # (kind 'custom': passed straight to _update_landcover_array); width % 4 = 1, 2, 3, one row, one pixel.
+              # No year offset that wraps: numpy 2 refuses to store a class outside 0..255 into the uint8 array.
+              dict(name='l_wide_edge_forest', seed=101, H=37, W=45, year=2021, kind='standard', forest='edge'),
+              dict(name='l_wide_all_forest', seed=102, H=20, W=50, year=2155, kind='water heavy', forest='all'),
+              dict(name='l_wide_thr_zeros', seed=103, H=31, W=27, year=2000, thr='zeros', forest='edge'),
+              dict(name='l_wide_thr_tens', seed=104, H=16, W=19, year=2050, thr='tens', forest='all'),
+              dict(name='l_wide_thr_1991', seed=105, H=24, W=26, year=2099, thr='1991', forest='edge'),
+              dict(name='l_wide_thr_negative', seed=106, H=1, W=61, year=2001, thr='negative', forest='all'),
+              dict(name='l_wide_1x1', seed=110, H=1, W=1, year=2000, kind='standard', forest='all')]
 DEFAULT_FOREST = [20, 50, 111, 113, 115, 116, 121, 123, 125, 126]
 
 
@@ -607,10 +618,17 @@ def gen_landcover(ref):
     """Replays create_landcover_mask :994-1115 on already-warped arrays with the
     reference's own helpers (the two gdal.Warp calls are the part that cannot run here)."""
     from proteus_amd.synth import synth_landcover_inputs
+    from oracle import land_inputs
     cls = ref.dswx_hls_landcover_classes_dict
     for case in LAND_CASES:
-        wc, cg = synth_landcover_inputs(case['tile'], case['H'], case['W'])
-        forest_classes = case.get('forest', DEFAULT_FOREST)
+        if 'seed' in case:
+            rng = np.random.default_rng(case['seed'])
+            wc = land_inputs.worldcover(rng, case['H'], case['W'], 'dense')
+            cg = land_inputs.copernicus(rng, case['H'], case['W'])
+            forest_classes = land_inputs.FOREST_SETS[case['forest']]
+        else:
+            wc, cg = synth_landcover_inputs(case['tile'], case['H'], case['W'])
+            forest_classes = case.get('forest', DEFAULT_FOREST)
         water = ref.decimate_by_summation(np.isin(wc, [80, 90, 95]).astype(np.uint8), 3, 3)
         urban = ref.decimate_by_summation((wc == 50).astype(np.uint8), 3, 3)
         tree = ref.decimate_by_summation((wc == 10).astype(np.uint8), 3, 3)
@@ -619,7 +637,10 @@ def gen_landcover(ref):
             forest |= (cg == c)
         tree = np.where(forest, tree, 0)
         land = np.full(water.shape, cls['fill_value'], dtype=np.uint8)
-        thr = ref.landcover_threshold_dict[case['kind']]
+        if 'thr' in case:
+            kind, thr = 'custom', list(land_inputs.THRESHOLD_SETS[case['thr']])
+        else:
+            kind, thr = case['kind'], ref.landcover_threshold_dict[case['kind']]
         off = case['year'] - 2000
         ref._update_landcover_array(land, tree, thr[0], cls['evergreen_forest'])
         ref._update_landcover_array(land, urban, thr[1], cls['low_intensity_developed_offset'] + off)
@@ -628,7 +649,7 @@ def gen_landcover(ref):
         np.savez_compressed(os.path.join(GOLDEN, f"land_{case['name']}.npz"), worldcover_up3=wc,
                             copernicus=cg, forest_classes=np.array(forest_classes, dtype=np.int32),
                             thresholds=np.array(thr, dtype=np.int32), year=np.array(case['year']),
-                            kind=np.array(case['kind']), land=land)
+                            kind=np.array(kind), land=land)
         u, c = np.unique(land, return_counts=True)
         print('land', case['name'], dict(zip(u.tolist(), c.tolist())))
 

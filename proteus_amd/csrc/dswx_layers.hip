@@ -754,9 +754,10 @@ static int land_args(LandArgs* a, int64_t height, int64_t width, const int32_t* 
         if (c >= 0 && c <= 255) a->forest_bits[c >> 5] |= 1u << (c & 31);
     }
     a->thr_tree = thresholds[0]; a->thr_low = thresholds[1]; a->thr_high = thresholds[2]; a->thr_water = thresholds[3];
-    // numpy stores the class through a uint8 array: values wrap modulo 256
-    a->low_class = (int)(uint8_t)(0 + year_offset);
-    a->high_class = (int)(uint8_t)(100 + year_offset);
+    // numpy stores the class through a uint8 array: values wrap modulo 256 (the reference's pinned numpy 1.23.5 wraps;
+    // numpy 2 raises OverflowError instead).  Unsigned sums: 100 + INT32_MAX must wrap, not overflow.
+    a->low_class = (int)(uint8_t)(0u + (uint32_t)year_offset);
+    a->high_class = (int)(uint8_t)(100u + (uint32_t)year_offset);
     a->height = height; a->width = width;
     return DSWX_OK;
 }

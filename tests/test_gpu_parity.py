@@ -1622,7 +1622,9 @@ def test_browse_layer_cover_mode(ctx):
     assert np.array_equal(got['browse'], o.compute_browse_array(raw, True, True))
 
 
-@pytest.mark.parametrize('name', ['l_standard', 'l_water_heavy', 'l_no_forest', 'l_odd'])
+@pytest.mark.parametrize('name', ['l_standard', 'l_water_heavy', 'l_no_forest', 'l_odd', 'l_wide_edge_forest',
+                                  'l_wide_all_forest', 'l_wide_thr_zeros', 'l_wide_thr_tens', 'l_wide_thr_1991',
+                                  'l_wide_thr_negative', 'l_wide_1x1'])
 def test_landcover_mask_golden(ctx, name):
     z = G.load(f'land_{name}.npz')
     got = ctx.landcover_mask(z['worldcover_up3'], z['copernicus'], z['forest_classes'].tolist(),

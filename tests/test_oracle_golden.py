@@ -184,13 +184,39 @@ def test_browse_tables():
         assert np.array_equal(got, z[key]), key
 
 
-@pytest.mark.parametrize('name', ['l_standard', 'l_water_heavy', 'l_no_forest', 'l_odd'])
+LAND_GOLDENS = ['l_standard', 'l_water_heavy', 'l_no_forest', 'l_odd', 'l_wide_edge_forest', 'l_wide_all_forest',
+                'l_wide_thr_zeros', 'l_wide_thr_tens', 'l_wide_thr_1991', 'l_wide_thr_negative', 'l_wide_1x1']
+
+
+@pytest.mark.parametrize('name', LAND_GOLDENS)
 def test_landcover_mask(name):
     z = G.load(f'land_{name}.npz')
-    got = o.landcover_mask_from_warped(z['worldcover_up3'], z['copernicus'],
-                                       z['forest_classes'].tolist(), str(z['kind']), int(z['year']))
-    assert np.array_equal(got, z['land'])
-    assert o.LANDCOVER_THRESHOLDS[str(z['kind'])] == z['thresholds'].tolist()
+    args = (z['worldcover_up3'], z['copernicus'], z['forest_classes'].tolist())
+    kind = str(z['kind'])
+    if kind == 'custom':     # thresholds the reference never ships, passed straight to _update_landcover_array
+        assert z['thresholds'].tolist() not in list(o.LANDCOVER_THRESHOLDS.values())
+    else:
+        assert o.LANDCOVER_THRESHOLDS[kind] == z['thresholds'].tolist()
+        assert np.array_equal(o.landcover_mask_from_warped(*args, kind, int(z['year'])), z['land'])
+    got = o.landcover_mask_from_warped(*args, year=int(z['year']), thresholds=z['thresholds'].tolist())
+    assert got.dtype == np.uint8 and np.array_equal(got, z['land'])
+
+
+def test_landcover_golden_domains():
+    """The fixtures together reach what the LAND kernels can get wrong: every WorldCover and CGLS byte, the +-1
+    neighbours of the counted codes, each 3x3 count 0..9 of every code, width % 4 = 0..3, one row, one pixel."""
+    from oracle import land_inputs
+    wcs = [G.load(f'land_{n}.npz')['worldcover_up3'] for n in LAND_GOLDENS]
+    cgs = [G.load(f'land_{n}.npz')['copernicus'] for n in LAND_GOLDENS]
+    assert set(np.unique(np.concatenate([w.ravel() for w in wcs])).tolist()) == set(range(256))
+    assert set(np.unique(np.concatenate([c.ravel() for c in cgs])).tolist()) == set(range(256))
+    for k, name in enumerate(('water', 'urban', 'tree')):
+        seen = set()
+        for w in wcs:
+            seen |= set(np.unique(land_inputs.counts(w)[k]).tolist())
+        assert seen == set(range(10)), name
+    assert {c.shape[1] % 4 for c in cgs} == {0, 1, 2, 3}
+    assert (1, 1) in [c.shape for c in cgs] and any(c.shape[0] == 1 and c.shape[1] > 1 for c in cgs)
 
 
 def test_goldens_reproduce_from_reference(tmp_path):
