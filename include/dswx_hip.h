@@ -499,7 +499,9 @@ int dswx_cog_blocks_device(dswx_ctx_t* ctx, const void* plane, int32_t elem_byte
 /* The inverse for a file being read: `blocks` = every block of one plane of an image, inflated, in block order, each
  * block_height x block_width samples (tiles; or strips: block_width = width, the short last strip's slot padded), native
  * byte order; elem_bytes 1 / 2 / 4 with predictor 1 (none) or 2 (running sum in the sample's width), or elem_bytes 4 with
- * predictor 3 (Float32, TIFF Technical Note 3: what GDAL writes for a Float32 DEM with PREDICTOR=3).  -> plane [height][width]. */
+ * predictor 3 (Float32, TIFF Technical Note 3: what GDAL writes for a Float32 DEM with PREDICTOR=3).  -> plane [height][width].
+ * Predictor 3 goes through a scratch of the context: such calls of one context are ordered across streams (a call on
+ * another stream than the previous one waits for it, as the classifier's launches do); predictors 1 and 2 are not. */
 int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, int64_t height, int64_t width,
                        int32_t block_width, int32_t block_height, int32_t predictor, void* plane, void* stream);
 /* One separable pass of the CUBICSPLINE overview convolution `save_as_cog` asks GDAL for on non-integer layers

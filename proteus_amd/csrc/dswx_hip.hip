@@ -503,10 +503,11 @@ int dswx_ctx_destroy(dswx_ctx_t* ctx) {
     return DSWX_OK;
 }
 
+}  // extern "C"
 
 // One launch of a context at a time on the GPU (dswx_host.h: the workspaces are shared): a call on another stream than
 // the previous call's waits for it.  The steady state -- every call on one stream -- costs nothing.
-static int dswx_ws_enter(dswx_ctx* ctx, hipStream_t s) {
+int dswx_ws_enter(dswx_ctx* ctx, hipStream_t s) {
     if (ctx->ws_used && ctx->ws_last != s) {
         if (!ctx->ws_event) HIP_TRY(hipEventCreateWithFlags(&ctx->ws_event, hipEventDisableTiming));
         // the context's own stream is alive as long as the context: mark its work now; a caller's stream may be gone by
@@ -516,7 +517,7 @@ static int dswx_ws_enter(dswx_ctx* ctx, hipStream_t s) {
     }
     return DSWX_OK;
 }
-static int dswx_ws_leave(dswx_ctx* ctx, hipStream_t s) {
+int dswx_ws_leave(dswx_ctx* ctx, hipStream_t s) {
     if (s != ctx->stream) {
         if (!ctx->ws_event) HIP_TRY(hipEventCreateWithFlags(&ctx->ws_event, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(ctx->ws_event, s));
@@ -525,6 +526,8 @@ static int dswx_ws_leave(dswx_ctx* ctx, hipStream_t s) {
     ctx->ws_used = true;
     return DSWX_OK;
 }
+
+extern "C" {
 
 // height/width are only needed (and only trusted) in 'cover' mode; 0 = unknown
 static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_tiles, int64_t n_pixels,

@@ -23,8 +23,8 @@ struct dswx_ctx {
     unsigned long long* fold_acc = nullptr;
     size_t fold_bytes = 0;
     bool fold_clean = false;
-    // The workspaces of a context (tables, counter partials, fold accumulators, 'cover' scratch) are shared by all its
-    // launches.  Launches on ONE stream are ordered by the stream; a launch on a different stream than the previous one
+    // The workspaces of a context (tables, counter partials, fold accumulators, 'cover' scratch, the Float32 untile
+    // scratch) are shared by all its launches.  Launches on ONE stream are ordered by the stream; a launch on a different stream than the previous one
     // waits for it (dswx_ws_enter / dswx_ws_leave in dswx_hip.hip: an event recorded behind every launch on a caller's
     // stream, or on the context's own stream at the moment the stream changes) -- two launches of one context never
     // overlap on the GPU (the fold accumulators would otherwise be left non-zero for good).
@@ -74,6 +74,11 @@ struct dswx_ctx {
     int fused_variant = -1;  // -1 automatic = the table-driven kernel (every layout since round 6); 0 forces the direct
                              // kernel, 3 the table-driven one (lab A/B and the variant parity tests)
 };
+
+// Orders the launches that use the workspaces above across streams (dswx_hip.hip): enter before the first launch (and
+// before growing a workspace: its hipStreamSynchronize(s) then covers the other streams' work too), leave after the last.
+int dswx_ws_enter(dswx_ctx* ctx, hipStream_t s);
+int dswx_ws_leave(dswx_ctx* ctx, hipStream_t s);
 
 // records a printf-style message for dswx_last_error() and returns `code`
 int dswx_fail(int code, const char* fmt, ...);

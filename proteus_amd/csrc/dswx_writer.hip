@@ -401,7 +401,11 @@ int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, 
     if ((long long)block_width * elem_bytes > 2147483647LL / 4) return dswx_fail(DSWX_ERR_ARG, "block too wide");
     if (predictor == 3) {
         // (1) the byte-wise running sum over every block row (4 bw bytes) -- the integer kernel on a "raster" of
-        // block_rows x 4 bw bytes that is one block -- into a scratch of the context, (2) the byte planes back into samples
+        // block_rows x 4 bw bytes that is one block -- into a scratch of the context, (2) the byte planes back into samples.
+        // The scratch is shared by every call of the context: a call on another stream than the previous user's waits for
+        // it (dswx_host.h), and does so before the grow below frees the buffer that call may still read
+        if (height > 65535) return dswx_fail(DSWX_ERR_ARG, "raster too tall for one launch");
+        if (int wrc = dswx_ws_enter(ctx, s)) return wrc;
         const size_t need = (size_t)a.block_rows * (size_t)block_width * 4;
         if (need > ctx->untile_bytes) {
             HIP_TRY(hipStreamSynchronize(s));
@@ -419,13 +423,12 @@ int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, 
         if (groups > 0x7fffffffull) return dswx_fail(DSWX_ERR_ARG, "raster too large for one launch");
         hipLaunchKernelGGL(dswx_untile_v1<unsigned char>, dim3((unsigned)groups), dim3(256), 0, s, b);
         HIP_TRY(hipGetLastError());
-        if (height > 65535) return dswx_fail(DSWX_ERR_ARG, "raster too tall for one launch");
         Fp3Args g = {};
         g.acc = static_cast<const unsigned char*>(ctx->untile_tmp); g.dst = static_cast<unsigned*>(plane);
         g.height = (int)height; g.width = (int)width; g.bw = block_width; g.bh = block_height; g.across = a.across;
         hipLaunchKernelGGL(dswx_untile_fp3_gather, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, s, g);
         HIP_TRY(hipGetLastError());
-        return DSWX_OK;
+        return dswx_ws_leave(ctx, s);
     }
     const unsigned long long groups = ((unsigned long long)a.block_rows + 3) / 4;
     if (groups > 0x7fffffffull) return dswx_fail(DSWX_ERR_ARG, "raster too large for one launch");
