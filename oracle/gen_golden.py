@@ -22,6 +22,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from oracle._ref_import import import_reference  # noqa: E402
 from proteus_amd.synth import synth_tile          # noqa: E402
+from oracle import band_inputs                     # noqa: E402
 
 # DSWX_GOLDEN_OUT: write somewhere else (tests/test_oracle_golden.py::test_goldens_reproduce_from_reference regenerates
 # into a temporary directory and compares with the committed fixtures)
@@ -208,6 +209,38 @@ def gen_diag(ref):
     print('diag_vectors.npz', vec.shape[0], 'vectors')
 
 
+def gen_diag_wide(ref):
+    """diag_vectors_wide.npz: what a caller with the clip off can pass -- negatives down to -32768 on every band, every
+    int16 sum overflowing in both directions, n / 0 with a negative n and 0 / 0 (also -32768 + -32768, which wraps to 0)."""
+    rng = np.random.default_rng(20261016)
+    e = np.array(band_inputs.EDGES, np.int16)
+    parts = [rng.integers(-32768, 32768, size=(2500, 6)),                     # uniform, negatives included
+             rng.choice(e, size=(2000, 6))]                                   # the edge values, every combination kind
+    # the four sums g + s1, n + r, g + r, n + s1 (and g - s1, n - r) past +32767 and below -32768
+    hi = rng.integers(16384, 32768, size=(1500, 6))
+    lo = rng.integers(-32768, -16383, size=(1500, 6))
+    parts += [hi, lo, np.where(rng.random((1500, 6)) < 0.5, hi, lo)]
+    # zero denominators: s1 = -g and r = -n (g, n of either sign), both zero, and -32768 twice
+    z = rng.integers(-32768, 32768, size=(1000, 6))
+    z[:, 4] = np.clip(-z[:, 1], -32768, 32767)
+    z[:, 2] = np.clip(-z[:, 3], -32768, 32767)
+    z[::7, 1] = z[::7, 4] = 0
+    z[3::7, 3] = z[3::7, 2] = 0
+    z[5::7, 1] = z[5::7, 4] = -32768
+    z[6::7, 3] = z[6::7, 2] = -32768
+    parts.append(z)
+    vec = np.concatenate(parts, axis=0).astype(np.int16)
+    out = {'bands': vec}
+    cols = [np.ascontiguousarray(vec[:, i]).reshape(1, -1) for i in range(6)]
+    with np.errstate(all='ignore'):
+        for tag, kw in ALT_THRESHOLDS.items():
+            thr = make_thresholds(ref, **kw)
+            out['diag_' + tag] = ref._compute_diagnostic_tests(*cols, thr)
+            out['thr_' + tag] = np.array([getattr(thr, k) for k in THR_KEYS], dtype=np.float64)
+    np.savez_compressed(os.path.join(GOLDEN, 'diag_vectors_wide.npz'), **out)
+    print('diag_vectors_wide.npz', vec.shape[0], 'vectors')
+
+
 THR_KEYS = ('wigt', 'awgt', 'pswt_1_mndwi', 'pswt_1_nir', 'pswt_1_swir1',
             'pswt_1_ndvi', 'pswt_2_mndwi', 'pswt_2_blue', 'pswt_2_nir',
             'pswt_2_swir1', 'pswt_2_swir2', 'lcmask_nir')
@@ -330,6 +363,25 @@ TILE_CASES = [
          domains=dict(land='0..255', shad='0..255', ocean='0..255')),
     dict(name='t160x112_cover_wide', tile=30, H=160, W=112, land=1, shad=1, ocean=1, mode='cover',
          domains=dict(land='0..255', shad='0..255', ocean='0/255')),
+    # the six int16 band planes over their whole range (oracle/band_inputs.py, its own stream per case): uniform int16
+    # with every LAND class (200, 201, < 100, 100..199) and SHAD zeros, so that the nir rules of A9 / A10 fire; 1..32767
+    # (every int16 sum wraps) with the fractional thresholds; the edge values with the zero_max fills; a per-pixel mix
+    # in 'cover' mode; a ragged tile (H * W % 8 = 5).  The reference always clips: the product configuration.
+    dict(name='t96_band_int16_masks', tile=31, H=96, W=96, land=1, shad=1, ocean=1, bands='int16',
+         domains=dict(land='0..255')),
+    dict(name='t96_band_positive_fractional', tile=32, H=96, W=96, land=1, shad=1, thr='fractional', bands='positive'),
+    dict(name='t96_band_edges_fills_zero_max', tile=33, H=96, W=96, land=1, ocean=1, fills='zero_max', bands='edges'),
+    dict(name='t96_band_mix_cover', tile=34, H=96, W=96, land=1, shad=1, ocean=1, mode='cover', bands='mix'),
+    dict(name='t97x61_band_int16_ragged', tile=35, H=97, W=61, land=1, shad=1, ocean=1, bands='int16'),
+    # the float32 chain (flag_offset_and_scale_inputs) at full range: offsets inside the data, scales that are not
+    # powers of two, pixels at the offsets and pairs that cancel (+-inf, NaN indices); then a negative and a zero scale.
+    # Every scale, offset and threshold is a float32 value range-wise, so numpy 1.23.5's value-based promotion and
+    # numpy 2's weak Python scalars both compute the chain in float32: the fixture holds for either.
+    dict(name='t64_band_f32_ties', tile=36, H=64, W=64, land=1, shad=1, ocean=1, bands='f32_ties',
+         scale=[(2.75e-5, 1000.0), (3.0, 1000.0), (2.75e-5, 16384.0), (2.75e-5, 16384.0), (3.0, 1000.0),
+                (3.0, 16384.0)]),
+    dict(name='t64_band_f32_neg_zero_scale', tile=37, H=64, W=64, land=1, shad=1, bands='int16', thr='reflectance',
+         scale=[(-1e-4, 0.0), (0.0, 7.0), (1e-4, -30.5), (-2.75e-5, 1000.0), (0.0, 0.0), (1e-4, 16384.0)]),
 ]
 
 
@@ -406,6 +458,12 @@ def gen_tiles(ref):
         H, W = case['H'], case['W']
         s = synth_tile(case['tile'], H, W, with_masks=True)
         bands = [b.copy() for b in s['bands']]
+        if case.get('bands'):
+            brng = np.random.default_rng(4000 + case['tile'])     # (its own stream, as the fills and domains below)
+            thr_d = dict(zip(THR_KEYS, [getattr(make_thresholds(ref, **ALT_THRESHOLDS[case.get('thr', 'default')]), k)
+                                        for k in THR_KEYS]), aerosol_max_nir=1000)
+            bands = band_inputs.bands_in(case['bands'], brng, (H, W), recipe=bands, thr=thr_d,
+                                         scale_offset=case.get('scale'))
         fmask = s['fmask'].copy()
         band_fills = [-9999.0] * 6
         fmask_fill = 255.0
@@ -669,6 +727,7 @@ def main():
         gen_tables(ref)
     if 'diag' in which:
         gen_diag(ref)
+        gen_diag_wide(ref)
     if 'tiles' in which:
         gen_tiles(ref)
     if 'shadow' in which:

@@ -89,6 +89,18 @@ def test_diag_vectors_c(tag):
         assert np.array_equal(res[k], z[k].ravel(), equal_nan=True)
 
 
+@pytest.mark.parametrize('tag', ['default', 'fractional', 'zeros', 'thirds', 'reflectance'])
+def test_diag_vectors_wide_c(tag):
+    """diag_vectors_wide.npz: negatives down to -32768 on every band, every int16 sum overflowing both ways, n / 0 with
+    a negative n and 0 / 0 -- the clip-off domain."""
+    z = G.load('diag_vectors_wide.npz')
+    cols = [np.ascontiguousarray(z['bands'][:, i]) for i in range(6)]
+    p = _capi.make_params(dict(zip(G.THR_KEYS, z['thr_' + tag].tolist())), band_fills=[None] * 6, fmask_fill=None,
+                          clip_negative_reflectance=False)
+    res = c_oracle.classify(p, cols, np.zeros(cols[0].shape, dtype=np.uint8), layers=('diag',))
+    assert np.array_equal(res['diag'], binary_repr(z['diag_' + tag].ravel()))
+
+
 def _predicate_job(args):
     t, lt, lo, hi = args
     return c_oracle.check_quotient_predicate(t, lt, lo, hi)

@@ -69,19 +69,23 @@ class Env:
         return ev
 
     def _calibrate(self, s):
-        rate = None
-        for cycles in (1 << 22, None):
-            if cycles is None:                       # second sample: ~60 ms at the first estimate
-                cycles = int(rate * 60.0)
+        """Spin cycles per millisecond at the FASTEST clock seen.  The spin counts shader clock cycles, so a hold lasts
+        cycles / (the clock while it runs): sized at a slow clock (an idle GPU ramping up, or a short first sample that
+        is mostly launch latency) it ends early once the clock rises, and a held call then runs during its 'hold'.
+        So: the first sample only wakes the GPU, the next three (~60 ms each) are timed, the highest rate is kept."""
+        rate, best = None, 0.0
+        for k in range(4):
+            cycles = 1 << 22 if rate is None else int(rate * 60.0)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(s)
             with torch.cuda.stream(s):
                 torch.cuda._sleep(cycles)
             e1.record(s)
             e1.synchronize()
-            r = cycles / max(e0.elapsed_time(e1), 1e-3)
-            rate = r if rate is None else min(rate, r)
-        return rate * 1.5                            # margin: the spin counts clock cycles, the clock may rise
+            rate = cycles / max(e0.elapsed_time(e1), 1e-3)
+            if k:
+                best = max(best, rate)
+        return best * 1.5                            # margin: the clock may rise past the fastest sample
 
     def _visible_during_hold(self, held, stream_arg):
         """Does a small kernel launched on `stream_arg` (a to_byte conversion into page-locked memory) finish, and its

@@ -80,6 +80,23 @@ def test_diag_vectors(tag):
     assert np.array_equal(o.compute_diagnostic_tests(*cols, thr), z['diag_' + tag])
 
 
+@pytest.mark.parametrize('tag', ['default', 'fractional', 'zeros', 'thirds', 'reflectance'])
+def test_diag_vectors_wide(tag):
+    z = G.load('diag_vectors_wide.npz')
+    cols = [np.ascontiguousarray(z['bands'][:, i]).reshape(1, -1) for i in range(6)]
+    thr = o.Thresholds(**dict(zip(G.THR_KEYS, z['thr_' + tag].tolist())))
+    assert np.array_equal(o.compute_diagnostic_tests(*cols, thr), z['diag_' + tag])
+    b = z['bands'].astype(np.int32)
+    # the domain the fixture claims: both ends of int16, sums past both ends, zero denominators (also by wrap)
+    assert b.min() == -32768 and b.max() == 32767 and (b.min(axis=0) == -32768).all()
+    for i, j in ((1, 4), (3, 2), (1, 2), (3, 4)):
+        assert ((b[:, i] + b[:, j]) > 32767).any() and ((b[:, i] + b[:, j]) < -32768).any(), (i, j)
+    for i, j in ((1, 4), (3, 2)):
+        d = (b[:, i] + b[:, j]).astype(np.int16)
+        assert ((d == 0) & ((b[:, i] - b[:, j]).astype(np.int16) < 0)).any() and ((b[:, i] == 0) & (b[:, j] == 0)).any()
+        assert ((b[:, i] == -32768) & (b[:, j] == -32768)).any()
+
+
 def test_survey_known_answers():
     """(blue..swir2) -> DIAG decimal / saved DIAG / WTR-1."""
     kats = [((300, 400, 300, 200, 100, 50), 31, 11111, 1),
