@@ -62,10 +62,6 @@ PlaneSet planes_of(uint32_t flags) {
     return s;
 }
 
-inline int elem_bytes(int plane) {
-    return (plane <= DSWX_PLANE_BAND0 + 5 || plane == DSWX_PLANE_DIAG) ? 2 : 1;
-}
-
 int layout_mode(uint32_t flags, uint32_t* mode) {
     *mode = flags & (DSWX_BATCH_SEPARATE_OUTPUTS | DSWX_BATCH_SLIDING_OUTPUTS);
     if (*mode == (DSWX_BATCH_SEPARATE_OUTPUTS | DSWX_BATCH_SLIDING_OUTPUTS))
@@ -95,26 +91,10 @@ struct dswx_batch {
 static void set_note(dswx_batch* b, const std::string& text) { b->note = text; }
 
 static void bind_structs(const dswx_batch* b, dswx_planes_in_t* in, dswx_planes_out_t* out) {
-    if (in) {
-        memset(in, 0, sizeof *in);
-        for (int k = 0; k < 6; ++k) in->band[k] = (const int16_t*)b->ptr[DSWX_PLANE_BAND0 + k];
-        in->fmask = (const uint8_t*)b->ptr[DSWX_PLANE_FMASK];
-        in->land = (const uint8_t*)b->ptr[DSWX_PLANE_LAND];
-        in->shad = (const uint8_t*)b->ptr[DSWX_PLANE_SHAD];
-        in->ocean = (const uint8_t*)b->ptr[DSWX_PLANE_OCEAN];
-    }
-    if (out) {
-        memset(out, 0, sizeof *out);
-        out->diag = (uint16_t*)b->ptr[DSWX_PLANE_DIAG];
-        out->wtr1 = (uint8_t*)b->ptr[DSWX_PLANE_WTR1];
-        out->wtr1_aerosol = (uint8_t*)b->ptr[DSWX_PLANE_WTR1_AEROSOL];
-        out->wtr2 = (uint8_t*)b->ptr[DSWX_PLANE_WTR2];
-        out->wtr = (uint8_t*)b->ptr[DSWX_PLANE_WTR];
-        out->bwtr = (uint8_t*)b->ptr[DSWX_PLANE_BWTR];
-        out->conf = (uint8_t*)b->ptr[DSWX_PLANE_CONF];
-        out->cloud = (uint8_t*)b->ptr[DSWX_PLANE_CLOUD];
-        out->browse = (uint8_t*)b->ptr[DSWX_PLANE_BROWSE];
-    }
+    if (in) memset(in, 0, sizeof *in);
+    if (out) memset(out, 0, sizeof *out);
+    for (const dswx_plane_desc& d : DSWX_PLANES)
+        if (d.batch >= 0) dswx_plane_set(d, in, out, b->ptr[d.batch]);
 }
 
 extern "C" {
@@ -140,8 +120,8 @@ int dswx_batch_layout(const dswx_batch_geom_t* geom, uint32_t flags, dswx_batch_
         return dswx_fail(DSWX_ERR_ARG, "batch too large");
     const uint64_t px = (uint64_t)geom->n_tiles * (uint64_t)stride;
     const PlaneSet ps = planes_of(flags);
-    for (int k : ps.in) out->plane_bytes[k] = up256(px * elem_bytes(k));
-    for (int k : ps.out) out->plane_bytes[k] = up256(px * elem_bytes(k));
+    for (int k : ps.in) out->plane_bytes[k] = up256(px * DSWX_PLANES[k].bytes);
+    for (int k : ps.out) out->plane_bytes[k] = up256(px * DSWX_PLANES[k].bytes);
     out->plane_bytes[DSWX_PLANE_COUNTERS] = up256((uint64_t)geom->n_tiles * DSWX_N_COUNTERS * sizeof(int64_t));
 
     uint64_t cur = 0;

@@ -1,6 +1,8 @@
 // dswx_hip.hip -- MI355X (gfx950 / CDNA4) DSWx-HLS per-pixel classifier: the direct fused kernel,
-// the generic kernel, kernel dispatch and the core of the C-ABI
-// (context, parameters, device-pointer entry points, device plumbing).  Elsewhere:
+// the generic kernel, kernel dispatch (classify_device_impl and its named steps, the grow-only workspaces:
+// dswx_ws_reserve) and the core of the C-ABI (context, parameters, device-pointer entry points, device plumbing).
+// Elsewhere:
+//   dswx_host.h           the context, the plane table (DSWX_PLANES) every host loop over the planes walks
 //   dswx_device.h         per-pixel device functions (single source of truth of the chain)
 //   dswx_classify_lut.hip table-driven production kernel (+ dswx_tables.h)
 //   dswx_host_path.hip    dswx_classify_host (synchronous and pipelined), page-locked memory
@@ -483,11 +485,8 @@ int dswx_ctx_create(int device, dswx_ctx_t** out) {
 int dswx_ctx_destroy(dswx_ctx_t* ctx) {
     if (!ctx) return DSWX_OK;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    if (ctx->partials) (void)hipFree(ctx->partials);
-    if (ctx->fold_acc) (void)hipFree(ctx->fold_acc);
-    if (ctx->cover) (void)hipFree(ctx->cover);
-    if (ctx->untile_tmp) (void)hipFree(ctx->untile_tmp);
+    for (dswx_workspace& w : ctx->ws)
+        if (w.p) (void)hipFree(w.p);
     if (ctx->tables) (void)hipFree(ctx->tables);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->h2d_stream) (void)hipStreamDestroy(ctx->h2d_stream);
@@ -527,34 +526,202 @@ int dswx_ws_leave(dswx_ctx* ctx, hipStream_t s) {
     return DSWX_OK;
 }
 
-extern "C" {
+// Grow-only: a workspace that is large enough is left alone.  Otherwise wait for the work that may still use the old
+// allocation, free it, allocate the new size (dswx_host.h: every hipMalloc of the library under the VA mutex).
+int dswx_ws_reserve(dswx_workspace& w, size_t need, hipStream_t s, bool whole_device) {
+    if (need <= w.bytes) return DSWX_OK;
+    HIP_TRY(whole_device ? hipDeviceSynchronize() : hipStreamSynchronize(s));
+    if (w.p) HIP_TRY(hipFree(w.p));
+    w.p = nullptr; w.bytes = 0;
+    HIP_TRY(dswx_locked_malloc(&w.p, need));
+    w.bytes = need;
+    return DSWX_OK;
+}
 
+// ---- dswx_classify_device / _2d / _batch: the steps of classify_device_impl below, in the order it takes them
+
+// What one call decides once for all its chunks
+struct ClassifyPlan {
+    hipStream_t s;
+    bool cover;         // mask_adjacent_to_cloud_mode 'cover': stage 1 here, stages 2 + 3 in dswx_cover.hip
+    bool masks;         // any of LAND / SHAD / OCEAN given
+    bool lut;           // the table-driven kernel (always, unless the lab forces the direct one: fused_variant = 0)
+    bool ragged;        // tiles start inside 8-pixel groups: dswx_classify_v1 does the < 8 + < 8 pixels at their edges
+    int lead_max;       // groups of per-tile lead-in of the table-driven kernel (dswx_lut_geometry)
+};
+
+// Step 1: the arguments.  Resolves tile_stride (0 = the tile) and derives the kernel parameter block.
 // height/width are only needed (and only trusted) in 'cover' mode; 0 = unknown
-static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_tiles, int64_t n_pixels,
-                                int64_t height, int64_t width, int64_t tile_stride, const dswx_planes_in_t* in,
-                                const dswx_planes_out_t* out, int64_t* counters, void* stream) {
+static int check_classify_args(const dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_tiles, int64_t n_pixels,
+                               int64_t height, int64_t width, int64_t* tile_stride, const dswx_planes_in_t* in,
+                               const dswx_planes_out_t* out, const int64_t* counters, DevParams* P) {
     if (!ctx || !params || !in || !out) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (n_tiles < 0 || n_pixels < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
-    if (tile_stride == 0) tile_stride = n_pixels;
-    if (tile_stride < n_pixels) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
+    if (*tile_stride == 0) *tile_stride = n_pixels;
+    if (*tile_stride < n_pixels) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
     for (int k = 0; k < 6; ++k)
         if (!in->band[k]) return dswx_fail(DSWX_ERR_ARG, "band[%d] is NULL", k);
     if (!in->fmask) return dswx_fail(DSWX_ERR_ARG, "fmask is NULL");
-    KArgs a = {};
-    int rc = dswx_make_dev_params(params, &a.P);
-    if (rc) return rc;
+    if (int rc = dswx_make_dev_params(params, P)) return rc;
     const bool cover = params->mask_adjacent_to_cloud_mode == DSWX_ADJ_COVER;
     if (cover && (height <= 0 || width <= 0 || height * width != n_pixels))
         return dswx_fail(DSWX_ERR_UNSUPPORTED,
                     "mask_adjacent_to_cloud_mode 'cover' is a 2-D neighbourhood operation: use "
                     "dswx_classify_device_2d / dswx_classify_host, which know the tile height and width");
     if (cover && (height > 2147483647LL || width > 2147483647LL)) return dswx_fail(DSWX_ERR_ARG, "tile too large");
-    for (int k = 0; k < 6; ++k)
-        if (!aligned_to(in->band[k], 2)) return dswx_fail(DSWX_ERR_ALIGN, "band[%d] not 2-byte aligned", k);
-    if (out->diag && !aligned_to(out->diag, 2)) return dswx_fail(DSWX_ERR_ALIGN, "diag not 2-byte aligned");
+    for (const dswx_plane_desc& d : DSWX_PLANES)       // the int16 bands and DIAG (the float64 planes: one-pixel kernel)
+        if (d.bytes == 2 && !aligned_to(dswx_plane_get(d, in, out), 2))
+            return dswx_fail(DSWX_ERR_ALIGN, "%s not 2-byte aligned", d.name);
     if (counters && !aligned_to(counters, 8)) return dswx_fail(DSWX_ERR_ALIGN, "counters not 8-byte aligned");
+    return DSWX_OK;
+}
+
+// Step 2, 'cover' mode only: sizes and grows the scratch, points stage 1 at it and takes away the layers that
+// stages 2 + 3 produce.
+static int bind_cover_scratch(dswx_ctx* ctx, KArgs& a, int64_t n_tiles, hipStream_t s) {
+    // scratch: one state byte per pixel (>= 256 bytes, it doubles as the slack IN FRONT of the bitmaps) +
+    // one bitmap dword per 8-pixel group + 64 dwords of slack behind them (the unconditional 16-byte row
+    // loads of stage 2) + the final snow bit plane
+    const size_t groups_per_tile = ((size_t)a.n_pixels + 7) / 8;
+    const size_t snow_dw_per_tile = ((size_t)a.n_pixels + 31) / 32 + 1;
+    const size_t state_bytes = (((size_t)n_tiles * (size_t)a.tile_stride + 255) & ~(size_t)255) + 256;
+    const size_t bits_bytes = ((size_t)n_tiles * groups_per_tile + 64) * 4;
+    const size_t need = state_bytes + bits_bytes + (size_t)n_tiles * snow_dw_per_tile * 4;
+    dswx_workspace& w = ctx->ws[dswx_ctx::WS_COVER];
+    if (int rc = dswx_ws_reserve(w, need, s)) return rc;
+    a.cover_state = static_cast<uint8_t*>(w.p);
+    a.cover_bits = reinterpret_cast<uint32_t*>(a.cover_state + state_bytes);
+    a.cover_bits_stride = (long long)groups_per_tile;
+    a.cover_snow = reinterpret_cast<uint32_t*>(a.cover_state + state_bytes + bits_bytes);
+    a.cover_snow_stride = (long long)snow_dw_per_tile;
+    // stage 1 stops before the snow step: these layers come from stages 2 + 3
+    a.out.wtr = a.out.bwtr = a.out.conf = a.out.cloud = a.out.browse = nullptr;
+    return DSWX_OK;
+}
+
+// Do all planes of the fused kernel START on 256-byte boundaries?  Then every tile of every plane has the same residue
+// modulo 256 pixels and the table-driven kernel can put every wave access on a line boundary: directly when the tile
+// stride is a multiple of 256 pixels (the padded batch layout), through its per-tile lead-in otherwise (contiguous
+// [n_tiles][H * W] arrays, the reference's natural layout: 3660 x 3660 = 144 mod 256) -- dswx_classify_lut.hip.
+static bool plane_bases_256(const dswx_planes_in_t* in, const dswx_planes_out_t* out) {
+    for (const dswx_plane_desc& d : DSWX_PLANES)
+        if (d.batch >= 0 && !aligned_to(dswx_plane_get(d, in, out), 256)) return false;
+    return true;
+}
+
+// Step 3, per chunk: every plane that is given moves on by `px` pixels (either struct may be NULL)
+static void shift_planes(dswx_planes_in_t* in, dswx_planes_out_t* out, int64_t px) {
+    for (const dswx_plane_desc& d : DSWX_PLANES)
+        if (char* p = dswx_plane_get(d, in, out)) dswx_plane_set(d, in, out, p + px * d.bytes);
+}
+
+// Step 4: where the fused kernel leaves its counts -- the fold accumulators (few tiles: the table-driven kernel sums the
+// counters itself, dswx_host.h: DSWX_FOLD_MAX_TILES) or per-wave partials for dswx_counters_finish.  (No vector launch
+// at all: the caller zeroes the counters for the atomic adds of the generic kernel.)
+static int bind_counters(dswx_ctx* ctx, KArgs& b, bool fold, bool extras, int64_t nt, int64_t gx, int waves, hipStream_t s) {
+    if (fold) {
+        // [tile][1 + groups of 2^gl blocks] accumulators, one 128-byte line each: zeroed when (re)allocated or after a
+        // failed launch, left zero by every launch that completes
+        dswx_workspace& w = ctx->ws[dswx_ctx::WS_FOLD];
+        const int gl = dswx_lut_fold_group_log2(extras);
+        const size_t need = (size_t)nt * (size_t)(1 + ((gx + (1LL << gl) - 1) >> gl)) * 128;
+        if (need > w.bytes) ctx->fold_clean = false;
+        if (int rc = dswx_ws_reserve(w, need, s)) return rc;
+        if (!ctx->fold_clean) {
+            // (rare: first use, growth, or after a failed launch.  Synchronous, so that a later call on ANOTHER
+            // stream of the caller's cannot overtake the zeroing)
+            HIP_TRY(hipMemsetAsync(w.p, 0, w.bytes, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            ctx->fold_clean = true;
+        }
+        b.fold_acc = static_cast<unsigned long long*>(w.p);
+        b.fold_group_log2 = gl;
+    } else if (b.counters) {
+        dswx_workspace& w = ctx->ws[dswx_ctx::WS_PARTIALS];
+        if (int rc = dswx_ws_reserve(w, (size_t)nt * (size_t)gx * waves * sizeof(uint2), s)) return rc;
+        b.partials = static_cast<uint2*>(w.p);
+    }
+    return DSWX_OK;
+}
+
+// The direct kernel (lab switch fused_variant = 0: A/B partner and variant parity tests)
+static void launch_direct(const dswx_ctx* ctx, const KArgs& b, bool masks, bool extras, dim3 grid, dim3 block, hipStream_t s,
+                          char* info, size_t info_len) {
+    if (b.P.f32_mode) {         // flag_offset_and_scale_inputs
+        if (masks && extras) hipLaunchKernelGGL((dswx_classify_v8<true, true, 4, true>), grid, block, 0, s, b);
+        else if (masks) hipLaunchKernelGGL((dswx_classify_v8<true, false, 4, true>), grid, block, 0, s, b);
+        else if (extras) hipLaunchKernelGGL((dswx_classify_v8<false, true, 4, true>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((dswx_classify_v8<false, false, 4, true>), grid, block, 0, s, b);
+    }
+    else if (masks && extras) hipLaunchKernelGGL((dswx_classify_v8<true, true>), grid, block, 0, s, b);
+    else if (masks) hipLaunchKernelGGL((dswx_classify_v8<true, false>), grid, block, 0, s, b);
+    else if (extras) hipLaunchKernelGGL((dswx_classify_v8<false, true>), grid, block, 0, s, b);
+    else if (ctx->tune_wps == 6) hipLaunchKernelGGL((dswx_classify_v8<false, false, 6>), grid, block, 0, s, b);
+    else if (ctx->tune_wps == 8) hipLaunchKernelGGL((dswx_classify_v8<false, false, 8>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((dswx_classify_v8<false, false, 4>), grid, block, 0, s, b);
+    snprintf(info, info_len, "dswx_classify_v8<%s,%s%s> (fused, direct stores) grid=(%lld,%lld) block=256",
+             masks ? "true" : "false", extras ? "true" : "false", b.P.f32_mode ? ",f32" : "", (long long)grid.x,
+             (long long)grid.y);
+}
+
+// Step 5: the `groups` whole 8-pixel groups of every tile of a chunk -- geometry, counters (step 4), the fused kernel
+// and, unless it folded them itself, the finishing kernel of the counters
+static int launch_fused(dswx_ctx* ctx, const ClassifyPlan& pl, KArgs& b, int64_t nt, int64_t groups, bool has_ocean,
+                        char* info, size_t info_len) {
+    // 'cover' stage 1 and the browse plane: the kernels' EXTRAS instantiations
+    const bool extras = pl.cover || b.out.browse;
+    int threads = 256;
+    long long gx = (groups + 255) / 256;
+    if (pl.lut) dswx_lut_geometry(ctx, groups, extras, pl.lead_max, &threads, &gx);
+    const int waves = threads / 64;
+    dim3 grid((unsigned)gx, (unsigned)nt), block(threads);
+    const bool fold = pl.lut && b.counters && nt <= DSWX_FOLD_MAX_TILES && b.n_pixels < (1LL << 24) && gx < 65536 &&
+                      ctx->tune_fold != 0;
+    if (int rc = bind_counters(ctx, b, fold, extras, nt, gx, waves, pl.s)) return rc;
+    if (pl.lut) {
+        if (int rc = dswx_lut_launch(ctx, b, pl.masks, grid, block, pl.s, info, info_len)) return rc;
+    } else {
+        launch_direct(ctx, b, pl.masks, extras, grid, block, pl.s, info, info_len);
+    }
+    if (hipError_t le = hipGetLastError(); le != hipSuccess) {
+        ctx->fold_clean = false;
+        return dswx_fail(DSWX_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(le));
+    }
+    if (b.counters && !fold) {
+        hipLaunchKernelGGL(dswx_counters_finish, dim3((unsigned)nt), dim3(1024), 0, pl.s, b.partials, b.counters,
+                           (long long)gx * waves, has_ocean ? 1 : 0, (long long)groups * 8,
+                           b.ragged ? b.in.fmask : nullptr, (long long)b.tile_stride, (long long)b.n_pixels);
+        HIP_TRY(hipGetLastError());
+    }
+    return DSWX_OK;
+}
+
+// Step 6: the pixels outside the whole groups, one per thread (dswx_classify_v1) -- the head and tail of every ragged
+// tile (16 threads of one block per tile), or the n_pixels % 8 tail from b.px_begin (the whole tile when it has no group)
+static int launch_edges(const KArgs& b, int64_t nt, int64_t groups, hipStream_t s, char* info, size_t info_len) {
+    if (b.ragged) {
+        hipLaunchKernelGGL(dswx_classify_v1, dim3(1, (unsigned)nt), dim3(256), 0, s, b);
+        const size_t len = strlen(info);
+        snprintf(info + len, info_len - len, " ragged tiles: edges by dswx_classify_v1");
+    } else if (b.px_begin < b.n_pixels) {
+        const int64_t gx = (b.n_pixels - b.px_begin + 255) / 256;
+        hipLaunchKernelGGL(dswx_classify_v1, dim3((unsigned)gx, (unsigned)nt), dim3(256), 0, s, b);
+        if (groups == 0)
+            snprintf(info, info_len, "dswx_classify_v1 grid=(%lld,%lld) block=256", (long long)gx, (long long)nt);
+    }
+    HIP_TRY(hipGetLastError());
+    return DSWX_OK;
+}
+
+static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_tiles, int64_t n_pixels,
+                                int64_t height, int64_t width, int64_t tile_stride, const dswx_planes_in_t* in,
+                                const dswx_planes_out_t* out, int64_t* counters, void* stream) {
+    KArgs a = {};
+    if (int rc = check_classify_args(ctx, params, n_tiles, n_pixels, height, width, &tile_stride, in, out, counters, &a.P))
+        return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    ClassifyPlan pl = {};
+    hipStream_t s = pl.s = stream ? (hipStream_t)stream : ctx->stream;
     if (n_tiles == 0 || n_pixels == 0) {
         if (counters && n_tiles > 0) HIP_TRY(hipMemsetAsync(counters, 0, (size_t)n_tiles * 3 * sizeof(int64_t), s));
         ctx->last_kernel = "none (empty input)";
@@ -566,39 +733,15 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
     a.counters = reinterpret_cast<unsigned long long*>(counters);
     a.n_pixels = n_pixels;
     a.tile_stride = tile_stride;
-    a.cover_state = nullptr; a.cover_bits = nullptr; a.cover_bits_stride = 0;
-    a.cover_snow = nullptr; a.cover_snow_stride = 0;
-    dswx_planes_out_t final_out = *out;     // what stages 2 + 3 of 'cover' write
     a.height = (int)height; a.width = (int)width;
-    if (cover) {
-        // scratch: one state byte per pixel (>= 256 bytes, it doubles as the slack IN FRONT of the bitmaps) +
-        // one bitmap dword per 8-pixel group + 64 dwords of slack behind them (the unconditional 16-byte row
-        // loads of stage 2) + the final snow bit plane
-        const size_t groups_per_tile = ((size_t)n_pixels + 7) / 8;
-        const size_t snow_dw_per_tile = ((size_t)n_pixels + 31) / 32 + 1;
-        const size_t state_bytes = (((size_t)n_tiles * (size_t)tile_stride + 255) & ~(size_t)255) + 256;
-        const size_t bits_bytes = ((size_t)n_tiles * groups_per_tile + 64) * 4;
-        const size_t need = state_bytes + bits_bytes + (size_t)n_tiles * snow_dw_per_tile * 4;
-        if (need > ctx->cover_bytes) {
-            HIP_TRY(hipStreamSynchronize(s));
-            if (ctx->cover) HIP_TRY(hipFree(ctx->cover));
-            ctx->cover = nullptr; ctx->cover_bytes = 0;
-            HIP_TRY(dswx_locked_malloc(&ctx->cover, need));
-            ctx->cover_bytes = need;
-        }
-        a.cover_state = static_cast<uint8_t*>(ctx->cover);
-        a.cover_bits = reinterpret_cast<uint32_t*>(a.cover_state + state_bytes);
-        a.cover_bits_stride = (long long)groups_per_tile;
-        a.cover_snow = reinterpret_cast<uint32_t*>(a.cover_state + state_bytes + bits_bytes);
-        a.cover_snow_stride = (long long)snow_dw_per_tile;
-        // stage 1 stops before the snow step: these layers come from stages 2 + 3
-        a.out.wtr = a.out.bwtr = a.out.conf = a.out.cloud = a.out.browse = nullptr;
-    }
+    pl.cover = params->mask_adjacent_to_cloud_mode == DSWX_ADJ_COVER;
+    if (pl.cover)
+        if (int rc = bind_cover_scratch(ctx, a, n_tiles, s)) return rc;
 
     const bool any_index = out->mndwi || out->ndvi || out->awesh;
     if (any_index && a.P.f32_mode)
         return dswx_fail(DSWX_ERR_UNSUPPORTED, "the float64 index planes describe the integer chain; not available with offset_and_scale_inputs");
-    const bool masks = in->land || in->shad || in->ocean;
+    pl.masks = in->land || in->shad || in->ocean;
     // Since round 6 BOTH vector kernels take ANY plane address and ANY tile stride: their 16- / 8-byte accesses go through
     // under-aligned vector types (dswx_device.h: u32x4_u, u32x2_u), for which the compiler emits the very same
     // global_load_dwordx4 / dwordx2 -- gfx950 performs unaligned global accesses in hardware, at a cost of 0 - 6 %
@@ -609,174 +752,43 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
     // alignment -- and ragged batches in 'cover' mode -- ran whole tiles on the 1-pixel-per-thread kernel at 0.17 of the
     // HBM peak (profiles/r05_generic_kernel_stats.csv); the direct kernel (dswx_classify_v8) stays behind the lab switch
     // fused_variant = 0 (A/B partner and variant parity tests).
-    const bool stride8 = (tile_stride % 8 == 0) || n_tiles == 1;
-    uint8_t* const u8outs[] = {out->wtr1, out->wtr1_aerosol, out->wtr2, out->wtr, out->bwtr, out->conf, out->cloud,
-                               out->browse};
-    // Do all planes START on 256-byte boundaries?  Then every tile of every plane has the same residue modulo 256
-    // pixels and the table-driven kernel can put every wave access on a line boundary: directly when the tile stride
-    // is a multiple of 256 pixels (the padded batch layout), through its per-tile lead-in otherwise (contiguous
-    // [n_tiles][H * W] arrays, the reference's natural layout: 3660 x 3660 = 144 mod 256) -- dswx_classify_lut.hip.
-    bool bases256 = true;
-    for (int k = 0; k < 6 && bases256; ++k) bases256 = aligned_to(in->band[k], 256);
-    bases256 = bases256 && aligned_to(in->fmask, 256) && (!in->land || aligned_to(in->land, 256)) &&
-               (!in->shad || aligned_to(in->shad, 256)) && (!in->ocean || aligned_to(in->ocean, 256)) &&
-               (!out->diag || aligned_to(out->diag, 256));
-    for (uint8_t* p : u8outs) bases256 = bases256 && (!p || aligned_to(p, 256));
-    const bool stride256 = (tile_stride % 256 == 0) || n_tiles == 1;
+    pl.lut = ctx->fused_variant != 0;
+    const bool bases256 = plane_bases_256(in, out);
     // ragged contiguous batches (H * W not a multiple of 8, several tiles): the table-driven kernel starts every tile at
     // its first 8-pixel boundary, the generic kernel does the < 8 + < 8 pixels at its edges (KArgs::ragged) -- with
     // 256-byte aligned bases that keeps every access of every tile aligned.  Not in 'cover' mode, whose bitmaps are indexed
     // by tile-relative 8-pixel groups (there, and for bases that are not aligned anyway, every tile starts at its pixel 0
     // and the accesses are unaligned); not when the direct kernel is forced.
-    const bool ragged = !stride8 && bases256 && !cover && ctx->fused_variant != 0;
-    const bool lut_ok = true;
+    pl.ragged = tile_stride % 8 != 0 && n_tiles != 1 && bases256 && !pl.cover && pl.lut;
     // the lead-in is a property of the addresses (correct for any of them); 0 only when every tile start is aligned
-    const int lead_max = (bases256 && stride256) ? 0 : 31;  // groups: dswx_lut_geometry
+    pl.lead_max = (bases256 && (tile_stride % 256 == 0 || n_tiles == 1)) ? 0 : 31;
 
     const int64_t max_y = 65535;
+    const int64_t groups = n_pixels >> 3;                      // (ragged: the most a tile can have)
     char info[256];
     for (int64_t t0 = 0; t0 < n_tiles; t0 += max_y) {
         const int64_t nt = (n_tiles - t0 < max_y) ? n_tiles - t0 : max_y;
         KArgs b = a;
         const int64_t shift = t0 * tile_stride;
-        for (int k = 0; k < 6; ++k) b.in.band[k] += shift;
-        b.in.fmask += shift;
-        if (b.in.land) b.in.land += shift;
-        if (b.in.shad) b.in.shad += shift;
-        if (b.in.ocean) b.in.ocean += shift;
-        if (b.out.diag) b.out.diag += shift;
-        if (b.out.wtr1) b.out.wtr1 += shift;
-        if (b.out.wtr1_aerosol) b.out.wtr1_aerosol += shift;
-        if (b.out.wtr2) b.out.wtr2 += shift;
-        if (b.out.wtr) b.out.wtr += shift;
-        if (b.out.bwtr) b.out.bwtr += shift;
-        if (b.out.conf) b.out.conf += shift;
-        if (b.out.cloud) b.out.cloud += shift;
-        if (b.out.browse) b.out.browse += shift;
-        if (b.out.mndwi) b.out.mndwi += shift;
-        if (b.out.ndvi) b.out.ndvi += shift;
-        if (b.out.awesh) b.out.awesh += shift;
+        shift_planes(&b.in, &b.out, shift);
         if (b.counters) b.counters += t0 * 3;
         if (b.cover_state) { b.cover_state += shift; b.cover_bits += t0 * b.cover_bits_stride; b.cover_snow += t0 * b.cover_snow_stride; }
-        b.px_begin = 0;
-        b.partials = nullptr;
-        b.fold_acc = nullptr;
-        b.fold_group_log2 = 0;
-        const int64_t groups = n_pixels >> 3;                      // (ragged: the most a tile can have)
-        b.ragged = (ragged && groups > 0) ? 1 : 0;
-        // the finishing kernel of the vector path WRITES the counters; only the generic kernel
-        // alone (atomic adds) needs them zeroed first
-        if (groups == 0 && b.counters)
-            HIP_TRY(hipMemsetAsync(b.counters, 0, (size_t)nt * 3 * sizeof(int64_t), s));
+        b.ragged = (pl.ragged && groups > 0) ? 1 : 0;
         if (groups > 0) {
-            // 'cover' stage 1 and the browse plane: the direct kernel or the table-driven one (3), not
-            // the experimental structures
-            const bool plain_outputs = !cover && !b.out.browse;
-            // automatic choice: the table-driven kernel, whatever the addresses (its per-tile lead-in takes care of
-            // strides that are not multiples of 256 pixels and of plane bases that are not 256-byte aligned)
-            int vsel = ctx->fused_variant;
-            if (vsel != 0 && vsel != 3) vsel = lut_ok ? 3 : 0;
-            const bool variant = vsel == 3;
-            int threads = 256;
-            long long gx_ll = (groups + 255) / 256;
-            if (variant) dswx_lut_geometry(ctx, groups, !plain_outputs, lead_max, &threads, &gx_ll);
-            const int64_t gx = gx_ll;
-            const int waves = threads / 64;
-            dim3 grid((unsigned)gx, (unsigned)nt), block(threads);
-            // few tiles: the table-driven kernel sums the counters itself (dswx_host.h: DSWX_FOLD_MAX_TILES)
-            const bool fold = variant && b.counters && nt <= DSWX_FOLD_MAX_TILES && n_pixels < (1LL << 24) && gx < 65536 &&
-                              ctx->tune_fold != 0;
-            if (fold) {
-                // [tile][1 + groups of 2^gl blocks] accumulators, one 128-byte line each: zeroed when (re)allocated or after a
-                // failed launch, left zero by every launch that completes
-                const int gl = dswx_lut_fold_group_log2(!plain_outputs);
-                const size_t need = (size_t)nt * (size_t)(1 + ((gx + (1LL << gl) - 1) >> gl)) * 128;
-                if (need > ctx->fold_bytes) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if (ctx->fold_acc) HIP_TRY(hipFree(ctx->fold_acc));
-                    ctx->fold_acc = nullptr; ctx->fold_bytes = 0;
-                    HIP_TRY(dswx_locked_malloc(&ctx->fold_acc, need));
-                    ctx->fold_bytes = need;
-                    ctx->fold_clean = false;
-                }
-                if (!ctx->fold_clean) {
-                    // (rare: first use, growth, or after a failed launch.  Synchronous, so that a later call on ANOTHER
-                    // stream of the caller's cannot overtake the zeroing)
-                    HIP_TRY(hipMemsetAsync(ctx->fold_acc, 0, ctx->fold_bytes, s));
-                    HIP_TRY(hipStreamSynchronize(s));
-                    ctx->fold_clean = true;
-                }
-                b.fold_acc = ctx->fold_acc;
-                b.fold_group_log2 = gl;
-            } else if (b.counters) {
-                const size_t need = (size_t)nt * (size_t)gx * waves * sizeof(uint2);
-                if (need > ctx->partials_bytes) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    if (ctx->partials) HIP_TRY(hipFree(ctx->partials));
-                    ctx->partials = nullptr; ctx->partials_bytes = 0;
-                    HIP_TRY(dswx_locked_malloc(&ctx->partials, need));
-                    ctx->partials_bytes = need;
-                }
-                b.partials = static_cast<uint2*>(ctx->partials);
-            }
-            if (variant) {
-                const int vrc = dswx_lut_launch(ctx, b, masks, grid, block, s, info, sizeof info);
-                if (vrc) return vrc;
-            } else {
-                const bool extras = b.out.browse || b.cover_state;
-                if (b.P.f32_mode) {         // flag_offset_and_scale_inputs
-                    if (masks && extras) hipLaunchKernelGGL((dswx_classify_v8<true, true, 4, true>), grid, block, 0, s, b);
-                    else if (masks) hipLaunchKernelGGL((dswx_classify_v8<true, false, 4, true>), grid, block, 0, s, b);
-                    else if (extras) hipLaunchKernelGGL((dswx_classify_v8<false, true, 4, true>), grid, block, 0, s, b);
-                    else hipLaunchKernelGGL((dswx_classify_v8<false, false, 4, true>), grid, block, 0, s, b);
-                }
-                else if (masks && extras) hipLaunchKernelGGL((dswx_classify_v8<true, true>), grid, block, 0, s, b);
-                else if (masks) hipLaunchKernelGGL((dswx_classify_v8<true, false>), grid, block, 0, s, b);
-                else if (extras) hipLaunchKernelGGL((dswx_classify_v8<false, true>), grid, block, 0, s, b);
-                else if (ctx->tune_wps == 6) hipLaunchKernelGGL((dswx_classify_v8<false, false, 6>), grid, block, 0, s, b);
-                else if (ctx->tune_wps == 8) hipLaunchKernelGGL((dswx_classify_v8<false, false, 8>), grid, block, 0, s, b);
-                else hipLaunchKernelGGL((dswx_classify_v8<false, false, 4>), grid, block, 0, s, b);
-                snprintf(info, sizeof info, "dswx_classify_v8<%s,%s%s> (fused, direct stores) grid=(%lld,%lld) block=256",
-                         masks ? "true" : "false", extras ? "true" : "false", b.P.f32_mode ? ",f32" : "", (long long)gx,
-                         (long long)nt);
-            }
-            if (hipError_t le = hipGetLastError(); le != hipSuccess) {
-                ctx->fold_clean = false;
-                return dswx_fail(DSWX_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(le));
-            }
-            if (b.counters && !fold) {
-                hipLaunchKernelGGL(dswx_counters_finish, dim3((unsigned)nt), dim3(1024), 0, s, b.partials,
-                                   b.counters, (long long)gx * waves, in->ocean ? 1 : 0, (long long)groups * 8,
-                                   b.ragged ? b.in.fmask : nullptr, (long long)tile_stride, (long long)n_pixels);
-                HIP_TRY(hipGetLastError());
-            }
+            if (int rc = launch_fused(ctx, pl, b, nt, groups, in->ocean != nullptr, info, sizeof info)) return rc;
             b.px_begin = groups * 8;
+        } else if (b.counters) {
+            // the finishing kernel of the vector path WRITES the counters; only the generic kernel
+            // alone (atomic adds) needs them zeroed first
+            HIP_TRY(hipMemsetAsync(b.counters, 0, (size_t)nt * 3 * sizeof(int64_t), s));
         }
-        if (b.ragged) {                     // head and tail pixels of every tile: 16 threads of one block per tile
-            hipLaunchKernelGGL(dswx_classify_v1, dim3(1, (unsigned)nt), dim3(256), 0, s, b);
-            const size_t len = strlen(info);
-            snprintf(info + len, sizeof info - len, " ragged tiles: edges by dswx_classify_v1");
-        } else if (b.px_begin < n_pixels) {
-            const int64_t rest = n_pixels - b.px_begin;
-            const int64_t gx = (rest + 255) / 256;
-            dim3 grid((unsigned)gx, (unsigned)nt), block(256);
-            hipLaunchKernelGGL(dswx_classify_v1, grid, block, 0, s, b);
-            if (groups == 0)
-                snprintf(info, sizeof info, "dswx_classify_v1 grid=(%lld,%lld) block=256",
-                         (long long)gx, (long long)nt);
-        }
-        HIP_TRY(hipGetLastError());
-        if (cover) {
+        if (int rc = launch_edges(b, nt, groups, s, info, sizeof info)) return rc;
+        if (pl.cover) {                     // stages 2 + 3 write the layers that were kept from stage 1
             KArgs c2 = b;
-            c2.out = final_out;
-            if (c2.out.wtr) c2.out.wtr += shift;
-            if (c2.out.bwtr) c2.out.bwtr += shift;
-            if (c2.out.conf) c2.out.conf += shift;
-            if (c2.out.cloud) c2.out.cloud += shift;
-            if (c2.out.browse) c2.out.browse += shift;
+            c2.out = *out;
+            shift_planes(nullptr, &c2.out, shift);
             const size_t len = strlen(info);
-            const int crc = dswx_cover_stage2_launch(ctx, c2, nt, s, info + len, sizeof info - len);
-            if (crc) return crc;
+            if (int crc = dswx_cover_stage2_launch(ctx, c2, nt, s, info + len, sizeof info - len)) return crc;
         }
         if (any_index) {
             dim3 grid((unsigned)((n_pixels + 255) / 256), (unsigned)nt), block(256);
@@ -787,6 +799,8 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
     ctx->last_kernel = info;
     return dswx_ws_leave(ctx, s);
 }
+
+extern "C" {
 
 int dswx_classify_device(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_tiles, int64_t n_pixels,
                          const dswx_planes_in_t* in, const dswx_planes_out_t* out, int64_t* counters,

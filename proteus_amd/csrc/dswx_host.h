@@ -4,24 +4,30 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <string>
 
 #include "dswx_device.h"
 
+// A grow-only device allocation of a context.
+struct dswx_workspace {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
 struct dswx_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
-    // grow-only staging for dswx_classify_host
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
-    // grow-only workspace for the vector kernel's per-wave counter partials
-    void* partials = nullptr;
-    size_t partials_bytes = 0;
-    // grow-only accumulators of the folded counters (launches of a few tiles, dswx_classify_lut.hip): zeroed when
-    // allocated, left zero by every launch that completes; a launch path that fails marks them dirty
-    unsigned long long* fold_acc = nullptr;
-    size_t fold_bytes = 0;
+    // The grow-only device workspaces (dswx_ws_reserve below), freed in a loop by dswx_ctx_destroy:
+    //   WS_STAGE    staging arena of dswx_classify_host (pageable planes: one tile; lab pipeline: three slots)
+    //   WS_PARTIALS the vector kernels' per-wave counter partials
+    //   WS_FOLD     accumulators of the folded counters (launches of a few tiles, dswx_classify_lut.hip): zeroed when
+    //                allocated, left zero by every launch that completes; a launch path that fails marks them dirty
+    //   WS_COVER    'cover' mode: state byte per pixel + bitmap dword per 8-pixel group + final snow bits
+    //   WS_UNTILE   dswx_untile_device for Float32 + floating-point predictor (the byte-wise running sums)
+    enum { WS_STAGE, WS_PARTIALS, WS_FOLD, WS_COVER, WS_UNTILE, WS_COUNT };
+    dswx_workspace ws[WS_COUNT];
     bool fold_clean = false;
     // The workspaces of a context (tables, counter partials, fold accumulators, 'cover' scratch, the Float32 untile
     // scratch) are shared by all its launches.  Launches on ONE stream are ordered by the stream; a launch on a different stream than the previous one
@@ -36,12 +42,6 @@ struct dswx_ctx {
     bool tables_valid = false;             // the device tables match tables_params, built on tables_stream
     hipStream_t tables_stream = nullptr;
     alignas(8) unsigned char tables_params[1024] = {};
-    // grow-only scratch of 'cover' mode: state byte per pixel + bitmap dword per 8-pixel group + final snow bits
-    void* cover = nullptr;
-    size_t cover_bytes = 0;
-    // grow-only scratch of dswx_untile_device for Float32 + floating-point predictor (the byte-wise running sums)
-    void* untile_tmp = nullptr;
-    size_t untile_bytes = 0;
     // pipelined host path (pinned host buffers): copy streams, per-slot events, pinned counter scratch
     hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
     hipEvent_t pipe_in[3] = {nullptr, nullptr, nullptr}, pipe_k[3] = {nullptr, nullptr, nullptr},
@@ -109,6 +109,63 @@ static inline hipError_t dswx_locked_malloc(T** p, size_t n) {
 }
 
 static inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// Grows workspace `w` of a context to at least `need` bytes (dswx_hip.hip): the one place a workspace is freed and
+// allocated again.  The free waits first for the work that may still use the old allocation: stream `s` (after
+// dswx_ws_enter that covers the context's work on other streams too), or the whole device.
+int dswx_ws_reserve(dswx_workspace& w, size_t need, hipStream_t s, bool whole_device = false);
+
+// ---- The 22 planes of a classify call: the pointers of dswx_planes_in_t, then those of dswx_planes_out_t, in ABI order
+// (for the first 19 that is the DSWX_PLANE_* numbering of the batch layout).  The ONE statement of which planes there
+// are, where their pointers live, how wide a pixel is and which are inputs; every host loop over "the planes" walks it.
+struct dswx_plane_desc {
+    const char* name;
+    bool input;               // a pointer of dswx_planes_in_t (else of dswx_planes_out_t)
+    unsigned char bytes;      // per pixel
+    signed char batch;        // DSWX_PLANE_* index; -1: not part of a batch (the float64 index planes)
+    unsigned short offset;    // of the pointer inside its struct
+};
+#define DSWX_BAND_(k) {"band[" #k "]", true, 2, DSWX_PLANE_BAND0 + k, offsetof(dswx_planes_in_t, band) + k * sizeof(void*)}
+#define DSWX_IN_(f, idx) {#f, true, 1, idx, offsetof(dswx_planes_in_t, f)}
+#define DSWX_OUT_(f, bytes, idx) {#f, false, bytes, idx, offsetof(dswx_planes_out_t, f)}
+constexpr dswx_plane_desc DSWX_PLANES[] = {
+    DSWX_BAND_(0), DSWX_BAND_(1), DSWX_BAND_(2), DSWX_BAND_(3), DSWX_BAND_(4), DSWX_BAND_(5),
+    DSWX_IN_(fmask, DSWX_PLANE_FMASK), DSWX_IN_(land, DSWX_PLANE_LAND), DSWX_IN_(shad, DSWX_PLANE_SHAD),
+    DSWX_IN_(ocean, DSWX_PLANE_OCEAN),
+    DSWX_OUT_(diag, 2, DSWX_PLANE_DIAG), DSWX_OUT_(wtr1, 1, DSWX_PLANE_WTR1),
+    DSWX_OUT_(wtr1_aerosol, 1, DSWX_PLANE_WTR1_AEROSOL), DSWX_OUT_(wtr2, 1, DSWX_PLANE_WTR2),
+    DSWX_OUT_(wtr, 1, DSWX_PLANE_WTR), DSWX_OUT_(bwtr, 1, DSWX_PLANE_BWTR), DSWX_OUT_(conf, 1, DSWX_PLANE_CONF),
+    DSWX_OUT_(cloud, 1, DSWX_PLANE_CLOUD), DSWX_OUT_(browse, 1, DSWX_PLANE_BROWSE),
+    DSWX_OUT_(mndwi, 8, -1), DSWX_OUT_(ndvi, 8, -1), DSWX_OUT_(awesh, 8, -1),
+};
+#undef DSWX_BAND_
+#undef DSWX_IN_
+#undef DSWX_OUT_
+constexpr int DSWX_N_PLANES = sizeof DSWX_PLANES / sizeof DSWX_PLANES[0];
+
+constexpr bool dswx_planes_in_abi_order() {     // every pointer of both structs, once, in order; batch index = position
+    constexpr int n_in = sizeof(dswx_planes_in_t) / sizeof(void*);
+    for (int i = 0; i < DSWX_N_PLANES; ++i) {
+        const dswx_plane_desc& d = DSWX_PLANES[i];
+        if (d.input != (i < n_in) || d.offset != (d.input ? i : i - n_in) * sizeof(void*)) return false;
+        if (d.batch != (i < DSWX_PLANE_COUNTERS ? i : -1)) return false;
+    }
+    return true;
+}
+static_assert(sizeof(dswx_planes_in_t) + sizeof(dswx_planes_out_t) == DSWX_N_PLANES * sizeof(void*) &&
+              dswx_planes_in_abi_order(), "DSWX_PLANES does not match dswx_planes_in_t / dswx_planes_out_t");
+
+// The pointer of plane `d` in an (in, out) pair, read and replaced as a plain address; a NULL struct has no planes.
+static inline char* dswx_plane_get(const dswx_plane_desc& d, const dswx_planes_in_t* in, const dswx_planes_out_t* out) {
+    const char* s = d.input ? reinterpret_cast<const char*>(in) : reinterpret_cast<const char*>(out);
+    char* p = nullptr;
+    if (s) std::memcpy(&p, s + d.offset, sizeof p);
+    return p;
+}
+static inline void dswx_plane_set(const dswx_plane_desc& d, dswx_planes_in_t* in, dswx_planes_out_t* out, const void* p) {
+    char* s = d.input ? reinterpret_cast<char*>(in) : reinterpret_cast<char*>(out);
+    if (s) std::memcpy(s + d.offset, &p, sizeof p);
+}
 
 // Launches of at most this many tiles sum the coverage counters inside the fused kernel (last-block-done) instead of in
 // the separate dswx_counters_finish launch, which is ~10 us + a kernel boundary: a quarter of a single-tile call, 0.09 % of

@@ -65,6 +65,57 @@ static bool is_pinned_host(const void* p) {
     return attr.type == hipMemoryTypeHost;
 }
 
+// The page-locked counter scratch of the context (zero copy: the kernels write it; staged pipeline: per-chunk counts),
+// grown to `rows` x 3 counters
+static int pipe_counters_reserve(dswx_ctx* ctx, size_t rows) {
+    if (rows <= ctx->pipe_counters_cap) return DSWX_OK;
+    if (ctx->pipe_counters) HIP_TRY(hipHostFree(ctx->pipe_counters));
+    ctx->pipe_counters = nullptr; ctx->pipe_counters_cap = 0;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->pipe_counters), rows * 3 * sizeof(int64_t)));
+    ctx->pipe_counters_cap = rows;
+    return DSWX_OK;
+}
+
+// One staging slot of the two copying paths: the planes that are given, `px` pixels of each, back to back in ABI order,
+// every plane rounded up to `round` bytes (a power of two); one 256-byte line for the counters behind them.
+struct StageSlot {
+    size_t off[DSWX_N_PLANES], o_cnt, bytes;
+};
+static StageSlot stage_layout(const dswx_planes_in_t* in, const dswx_planes_out_t* out, size_t px, size_t round) {
+    StageSlot L;
+    size_t off = 0;
+    for (int i = 0; i < DSWX_N_PLANES; ++i) {
+        L.off[i] = off;
+        if (dswx_plane_get(DSWX_PLANES[i], in, out)) off += (px * DSWX_PLANES[i].bytes + round - 1) & ~(round - 1);
+    }
+    L.o_cnt = off;
+    L.bytes = off + 256;
+    return L;
+}
+// Queues on `s` the upload of `n` pixels from pixel `hoff` of every input plane into the slot at `base`, and points
+// din / dout at the slot's planes
+static int stage_upload(const StageSlot& L, char* base, const dswx_planes_in_t* in, const dswx_planes_out_t* out, size_t hoff,
+                        size_t n, hipStream_t s, dswx_planes_in_t* din, dswx_planes_out_t* dout) {
+    for (int i = 0; i < DSWX_N_PLANES; ++i) {
+        const dswx_plane_desc& d = DSWX_PLANES[i];
+        const char* h = dswx_plane_get(d, in, out);
+        if (!h) continue;
+        if (d.input) HIP_TRY(hipMemcpyAsync(base + L.off[i], h + hoff * d.bytes, n * d.bytes, hipMemcpyHostToDevice, s));
+        dswx_plane_set(d, din, dout, base + L.off[i]);
+    }
+    return DSWX_OK;
+}
+// ... and the way back: `n` pixels of every output plane from the slot to pixel `hoff` of the host plane
+static int stage_download(const StageSlot& L, const char* base, const dswx_planes_out_t* out, size_t hoff, size_t n,
+                          hipStream_t s) {
+    for (int i = 0; i < DSWX_N_PLANES; ++i) {
+        const dswx_plane_desc& d = DSWX_PLANES[i];
+        char* h = d.input ? nullptr : dswx_plane_get(d, nullptr, out);
+        if (h) HIP_TRY(hipMemcpyAsync(h + hoff * d.bytes, base + L.off[i], n * d.bytes, hipMemcpyDeviceToHost, s));
+    }
+    return DSWX_OK;
+}
+
 // Zero-copy host path.  Page-locked host memory is mapped into the device's address space, so the
 // device-pointer entry can be handed the host planes as they are: the fused kernel's streaming loads become
 // PCIe reads, its streaming stores PCIe writes, and the link runs in both directions for the whole launch --
@@ -81,32 +132,11 @@ static int classify_host_zero_copy(dswx_ctx_t* ctx, const dswx_params_t* params,
     };
     dswx_planes_in_t din{};
     dswx_planes_out_t dout{};
-    for (int k = 0; k < 6; ++k) din.band[k] = static_cast<const int16_t*>(dev(in->band[k]));
-    din.fmask = static_cast<const uint8_t*>(dev(in->fmask));
-    din.land = static_cast<const uint8_t*>(dev(in->land));
-    din.shad = static_cast<const uint8_t*>(dev(in->shad));
-    din.ocean = static_cast<const uint8_t*>(dev(in->ocean));
-    dout.diag = static_cast<uint16_t*>(dev(out->diag));
-    dout.wtr1 = static_cast<uint8_t*>(dev(out->wtr1));
-    dout.wtr1_aerosol = static_cast<uint8_t*>(dev(out->wtr1_aerosol));
-    dout.wtr2 = static_cast<uint8_t*>(dev(out->wtr2));
-    dout.wtr = static_cast<uint8_t*>(dev(out->wtr));
-    dout.bwtr = static_cast<uint8_t*>(dev(out->bwtr));
-    dout.conf = static_cast<uint8_t*>(dev(out->conf));
-    dout.cloud = static_cast<uint8_t*>(dev(out->cloud));
-    dout.browse = static_cast<uint8_t*>(dev(out->browse));
-    dout.mndwi = static_cast<double*>(dev(out->mndwi));
-    dout.ndvi = static_cast<double*>(dev(out->ndvi));
-    dout.awesh = static_cast<double*>(dev(out->awesh));
+    for (const dswx_plane_desc& d : DSWX_PLANES) dswx_plane_set(d, &din, &dout, dev(dswx_plane_get(d, in, out)));
     if (err != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "hipHostGetDevicePointer: %s", hipGetErrorString(err));
     int64_t* dcnt = nullptr;
     if (counters) {          // the caller's counters may be pageable: a page-locked span of the context receives them
-        if ((size_t)n_tiles > ctx->pipe_counters_cap) {
-            if (ctx->pipe_counters) HIP_TRY(hipHostFree(ctx->pipe_counters));
-            ctx->pipe_counters = nullptr; ctx->pipe_counters_cap = 0;
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->pipe_counters), (size_t)n_tiles * 3 * sizeof(int64_t)));
-            ctx->pipe_counters_cap = (size_t)n_tiles;
-        }
+        if (int rc = pipe_counters_reserve(ctx, (size_t)n_tiles)) return rc;
         dcnt = static_cast<int64_t*>(dev(ctx->pipe_counters));
         if (err != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "hipHostGetDevicePointer: %s", hipGetErrorString(err));
     }
@@ -140,33 +170,12 @@ static int classify_host_pipelined(dswx_ctx_t* ctx, const dswx_params_t* params,
     chunk = (chunk + 2047) / 2048 * 2048;
     const int64_t per_tile = (P + chunk - 1) / chunk;
     const int64_t n_chunks = per_tile * n_tiles;
-    if ((size_t)n_chunks > ctx->pipe_counters_cap) {
-        if (ctx->pipe_counters) HIP_TRY(hipHostFree(ctx->pipe_counters));
-        ctx->pipe_counters = nullptr; ctx->pipe_counters_cap = 0;
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&ctx->pipe_counters), (size_t)n_chunks * 3 * sizeof(int64_t)));
-        ctx->pipe_counters_cap = (size_t)n_chunks;
-    }
-    // slot layout (offsets within one slot, all 256-byte aligned because chunk % 2048 == 0)
-    const uint8_t* const h_in_u8[4] = {in->fmask, in->land, in->shad, in->ocean};
-    uint8_t* const h_out_u8[8] = {out->wtr1, out->wtr1_aerosol, out->wtr2, out->wtr, out->bwtr, out->conf, out->cloud,
-                                  out->browse};
-    double* const h_f64[3] = {out->mndwi, out->ndvi, out->awesh};
-    size_t off = 0, o_band[6], o_in_u8[4], o_diag, o_out_u8[8], o_f64[3], o_cnt;
-    for (int k = 0; k < 6; ++k) { o_band[k] = off; off += (size_t)chunk * 2; }
-    for (int i = 0; i < 4; ++i) { o_in_u8[i] = off; if (h_in_u8[i]) off += (size_t)chunk; }
-    o_diag = off; if (out->diag) off += (size_t)chunk * 2;
-    for (int i = 0; i < 8; ++i) { o_out_u8[i] = off; if (h_out_u8[i]) off += (size_t)chunk; }
-    for (int i = 0; i < 3; ++i) { o_f64[i] = off; if (h_f64[i]) off += (size_t)chunk * 8; }
-    o_cnt = off; off += 256;
-    const size_t slot_bytes = off;
-    if (slot_bytes * NSLOT > ctx->stage_bytes) {
-        HIP_TRY(hipDeviceSynchronize());
-        if (ctx->stage) HIP_TRY(hipFree(ctx->stage));
-        ctx->stage = nullptr; ctx->stage_bytes = 0;
-        HIP_TRY(dswx_locked_malloc(&ctx->stage, slot_bytes * NSLOT));
-        ctx->stage_bytes = slot_bytes * NSLOT;
-    }
-    char* const arena = static_cast<char*>(ctx->stage);
+    if (int rc = pipe_counters_reserve(ctx, (size_t)n_chunks)) return rc;
+    // (no rounding: every plane of a slot is 256-byte aligned because chunk % 2048 == 0)
+    const StageSlot L = stage_layout(in, out, (size_t)chunk, 1);
+    dswx_workspace& stage = ctx->ws[dswx_ctx::WS_STAGE];
+    if (int rc = dswx_ws_reserve(stage, L.bytes * NSLOT, nullptr, true)) return rc;
+    char* const arena = static_cast<char*>(stage.p);
     hipStream_t sc = ctx->stream, sh = ctx->h2d_stream, sd = ctx->d2h_stream;
     bool slot_used[NSLOT] = {false, false, false};
     for (int64_t c = 0; c < n_chunks; ++c) {
@@ -174,41 +183,22 @@ static int classify_host_pipelined(dswx_ctx_t* ctx, const dswx_params_t* params,
         const int64_t tile = c / per_tile, px0 = (c % per_tile) * chunk;
         const int64_t n = (P - px0 < chunk) ? P - px0 : chunk;
         const size_t hoff = (size_t)tile * (size_t)P + (size_t)px0;
-        char* base = arena + slot_bytes * slot;
+        char* base = arena + L.bytes * slot;
         dswx_planes_in_t din{};
         dswx_planes_out_t dout{};
         // ---- upload (after the slot's previous download finished)
         if (slot_used[slot]) HIP_TRY(hipStreamWaitEvent(sh, ctx->pipe_out[slot], 0));
-        for (int k = 0; k < 6; ++k) {
-            HIP_TRY(hipMemcpyAsync(base + o_band[k], in->band[k] + hoff, (size_t)n * 2, hipMemcpyHostToDevice, sh));
-            din.band[k] = reinterpret_cast<const int16_t*>(base + o_band[k]);
-        }
-        const uint8_t** const d_in_u8[4] = {&din.fmask, &din.land, &din.shad, &din.ocean};
-        for (int i = 0; i < 4; ++i)
-            if (h_in_u8[i]) {
-                HIP_TRY(hipMemcpyAsync(base + o_in_u8[i], h_in_u8[i] + hoff, (size_t)n, hipMemcpyHostToDevice, sh));
-                *d_in_u8[i] = reinterpret_cast<const uint8_t*>(base + o_in_u8[i]);
-            }
+        if (int rc = stage_upload(L, base, in, out, hoff, (size_t)n, sh, &din, &dout)) return rc;
         HIP_TRY(hipEventRecord(ctx->pipe_in[slot], sh));
         // ---- classify
-        if (out->diag) dout.diag = reinterpret_cast<uint16_t*>(base + o_diag);
-        uint8_t** const d_out_u8[8] = {&dout.wtr1, &dout.wtr1_aerosol, &dout.wtr2, &dout.wtr, &dout.bwtr, &dout.conf,
-                                       &dout.cloud, &dout.browse};
-        for (int i = 0; i < 8; ++i) if (h_out_u8[i]) *d_out_u8[i] = reinterpret_cast<uint8_t*>(base + o_out_u8[i]);
-        double** const d_f64[3] = {&dout.mndwi, &dout.ndvi, &dout.awesh};
-        for (int i = 0; i < 3; ++i) if (h_f64[i]) *d_f64[i] = reinterpret_cast<double*>(base + o_f64[i]);
-        int64_t* dcnt = counters ? reinterpret_cast<int64_t*>(base + o_cnt) : nullptr;
+        int64_t* dcnt = counters ? reinterpret_cast<int64_t*>(base + L.o_cnt) : nullptr;
         HIP_TRY(hipStreamWaitEvent(sc, ctx->pipe_in[slot], 0));
         const int rc = dswx_classify_device(ctx, params, 1, n, &din, &dout, dcnt, sc);
         if (rc) { (void)hipDeviceSynchronize(); return rc; }
         HIP_TRY(hipEventRecord(ctx->pipe_k[slot], sc));
         // ---- download
         HIP_TRY(hipStreamWaitEvent(sd, ctx->pipe_k[slot], 0));
-        if (out->diag) HIP_TRY(hipMemcpyAsync(out->diag + hoff, dout.diag, (size_t)n * 2, hipMemcpyDeviceToHost, sd));
-        for (int i = 0; i < 8; ++i)
-            if (h_out_u8[i]) HIP_TRY(hipMemcpyAsync(h_out_u8[i] + hoff, *d_out_u8[i], (size_t)n, hipMemcpyDeviceToHost, sd));
-        for (int i = 0; i < 3; ++i)
-            if (h_f64[i]) HIP_TRY(hipMemcpyAsync(h_f64[i] + hoff, *d_f64[i], (size_t)n * 8, hipMemcpyDeviceToHost, sd));
+        if (int drc = stage_download(L, base, out, hoff, (size_t)n, sd)) return drc;
         if (counters)
             HIP_TRY(hipMemcpyAsync(ctx->pipe_counters + c * 3, dcnt, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, sd));
         HIP_TRY(hipEventRecord(ctx->pipe_out[slot], sd));
@@ -255,12 +245,7 @@ int dswx_classify_host(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_t
             return is_pinned_host(p) && is_pinned_host(static_cast<const char*>(p) + bytes - 1);
         };
         bool pinned = true;
-        for (int k = 0; k < 6 && pinned; ++k) pinned = ok_span(in->band[k], npx * 2);
-        const void* const rest[] = {in->fmask, in->land, in->shad, in->ocean, out->wtr1, out->wtr1_aerosol,
-                                    out->wtr2, out->wtr, out->bwtr, out->conf, out->cloud, out->browse};
-        for (const void* p : rest) pinned = pinned && ok_span(p, npx);
-        pinned = pinned && ok_span(out->diag, npx * 2) && ok_span(out->mndwi, npx * 8) &&
-                 ok_span(out->ndvi, npx * 8) && ok_span(out->awesh, npx * 8);
+        for (const dswx_plane_desc& d : DSWX_PLANES) pinned = pinned && ok_span(dswx_plane_get(d, in, out), npx * d.bytes);
         if (pinned && ctx->host_pipeline == 2) return classify_host_zero_copy(ctx, params, n_tiles, height, width, in, out, counters);
         if (pinned) return classify_host_pipelined(ctx, params, n_tiles, P, in, out, counters);
     }
@@ -272,58 +257,22 @@ int dswx_classify_host(dswx_ctx_t* ctx, const dswx_params_t* params, int64_t n_t
     // pages that are being faulted in, migrated or collapsed underneath were not reliable.  Pageable planes are copied.)
     // pageable host buffers (or 'cover' mode): one tile at a time through a grow-only device
     // arena: planes at 256-byte aligned offsets so the vector kernel is always eligible
-    auto rnd = [](size_t x) { return (x + 255) & ~size_t(255); };
-    size_t off = 0;
-    size_t o_band[6], o_fm, o_land = 0, o_shad = 0, o_ocean = 0;
-    for (int k = 0; k < 6; ++k) { o_band[k] = off; off += rnd((size_t)P * 2); }
-    o_fm = off; off += rnd((size_t)P);
-    if (in->land) { o_land = off; off += rnd((size_t)P); }
-    if (in->shad) { o_shad = off; off += rnd((size_t)P); }
-    if (in->ocean) { o_ocean = off; off += rnd((size_t)P); }
-    size_t o_diag = off; if (out->diag) off += rnd((size_t)P * 2);
-    uint8_t* const h_u8[8] = {out->wtr1, out->wtr1_aerosol, out->wtr2, out->wtr, out->bwtr, out->conf, out->cloud,
-                              out->browse};
-    size_t o_u8[8];
-    for (int i = 0; i < 8; ++i) { o_u8[i] = off; if (h_u8[i]) off += rnd((size_t)P); }
-    double* const h_f64[3] = {out->mndwi, out->ndvi, out->awesh};
-    size_t o_f64[3];
-    for (int i = 0; i < 3; ++i) { o_f64[i] = off; if (h_f64[i]) off += rnd((size_t)P * 8); }
-    size_t o_cnt = off; off += 256;
-    if (off > ctx->stage_bytes) {
-        if (ctx->stage) HIP_TRY(hipFree(ctx->stage));
-        ctx->stage = nullptr; ctx->stage_bytes = 0;
-        HIP_TRY(dswx_locked_malloc(&ctx->stage, off));
-        ctx->stage_bytes = off;
-    }
-    char* base = static_cast<char*>(ctx->stage);
     hipStream_t s = ctx->stream;
+    const StageSlot L = stage_layout(in, out, (size_t)P, 256);
+    // (every tile below ends in hipStreamSynchronize(s), so nothing of this path is in flight here: the stream the
+    // grow waits for is idle unless a caller's earlier work is still queued on it)
+    dswx_workspace& stage = ctx->ws[dswx_ctx::WS_STAGE];
+    if (int rc = dswx_ws_reserve(stage, L.bytes, s)) return rc;
+    char* base = static_cast<char*>(stage.p);
     for (int64_t t = 0; t < n_tiles; ++t) {
         const size_t sh = (size_t)t * (size_t)P;
         dswx_planes_in_t din{};
         dswx_planes_out_t dout{};
-        for (int k = 0; k < 6; ++k) {
-            HIP_TRY(hipMemcpyAsync(base + o_band[k], in->band[k] + sh, (size_t)P * 2, hipMemcpyHostToDevice, s));
-            din.band[k] = reinterpret_cast<const int16_t*>(base + o_band[k]);
-        }
-        HIP_TRY(hipMemcpyAsync(base + o_fm, in->fmask + sh, (size_t)P, hipMemcpyHostToDevice, s));
-        din.fmask = reinterpret_cast<const uint8_t*>(base + o_fm);
-        if (in->land) { HIP_TRY(hipMemcpyAsync(base + o_land, in->land + sh, (size_t)P, hipMemcpyHostToDevice, s)); din.land = reinterpret_cast<const uint8_t*>(base + o_land); }
-        if (in->shad) { HIP_TRY(hipMemcpyAsync(base + o_shad, in->shad + sh, (size_t)P, hipMemcpyHostToDevice, s)); din.shad = reinterpret_cast<const uint8_t*>(base + o_shad); }
-        if (in->ocean) { HIP_TRY(hipMemcpyAsync(base + o_ocean, in->ocean + sh, (size_t)P, hipMemcpyHostToDevice, s)); din.ocean = reinterpret_cast<const uint8_t*>(base + o_ocean); }
-        if (out->diag) dout.diag = reinterpret_cast<uint16_t*>(base + o_diag);
-        uint8_t** const d_u8[8] = {&dout.wtr1, &dout.wtr1_aerosol, &dout.wtr2, &dout.wtr, &dout.bwtr, &dout.conf, &dout.cloud,
-                                   &dout.browse};
-        for (int i = 0; i < 8; ++i) if (h_u8[i]) *d_u8[i] = reinterpret_cast<uint8_t*>(base + o_u8[i]);
-        double** const d_f64[3] = {&dout.mndwi, &dout.ndvi, &dout.awesh};
-        for (int i = 0; i < 3; ++i) if (h_f64[i]) *d_f64[i] = reinterpret_cast<double*>(base + o_f64[i]);
-        int64_t* dcnt = counters ? reinterpret_cast<int64_t*>(base + o_cnt) : nullptr;
+        if (int rc = stage_upload(L, base, in, out, sh, (size_t)P, s, &din, &dout)) return rc;
+        int64_t* dcnt = counters ? reinterpret_cast<int64_t*>(base + L.o_cnt) : nullptr;
         int rc = dswx_classify_device_2d(ctx, params, 1, height, width, &din, &dout, dcnt, s);
         if (rc) return rc;
-        if (out->diag) HIP_TRY(hipMemcpyAsync(out->diag + sh, dout.diag, (size_t)P * 2, hipMemcpyDeviceToHost, s));
-        for (int i = 0; i < 8; ++i)
-            if (h_u8[i]) HIP_TRY(hipMemcpyAsync(h_u8[i] + sh, *d_u8[i], (size_t)P, hipMemcpyDeviceToHost, s));
-        for (int i = 0; i < 3; ++i)
-            if (h_f64[i]) HIP_TRY(hipMemcpyAsync(h_f64[i] + sh, *d_f64[i], (size_t)P * 8, hipMemcpyDeviceToHost, s));
+        if (int drc = stage_download(L, base, out, sh, (size_t)P, s)) return drc;
         if (counters) HIP_TRY(hipMemcpyAsync(counters + t * 3, dcnt, 3 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }

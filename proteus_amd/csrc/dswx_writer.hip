@@ -407,16 +407,11 @@ int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, 
         if (height > 65535) return dswx_fail(DSWX_ERR_ARG, "raster too tall for one launch");
         if (int wrc = dswx_ws_enter(ctx, s)) return wrc;
         const size_t need = (size_t)a.block_rows * (size_t)block_width * 4;
-        if (need > ctx->untile_bytes) {
-            HIP_TRY(hipStreamSynchronize(s));
-            if (ctx->untile_tmp) HIP_TRY(hipFree(ctx->untile_tmp));
-            ctx->untile_tmp = nullptr; ctx->untile_bytes = 0;
-            HIP_TRY(dswx_locked_malloc(&ctx->untile_tmp, need));
-            ctx->untile_bytes = need;
-        }
+        dswx_workspace& tmp = ctx->ws[dswx_ctx::WS_UNTILE];
+        if (int rc = dswx_ws_reserve(tmp, need, s)) return rc;
         if (a.block_rows > 2147483647LL) return dswx_fail(DSWX_ERR_ARG, "raster too large for one launch");
         UntileArgs b = {};
-        b.blocks = blocks; b.dst = ctx->untile_tmp;
+        b.blocks = blocks; b.dst = tmp.p;
         b.height = (int)a.block_rows; b.width = 4 * block_width; b.bw = 4 * block_width; b.bh = (int)a.block_rows;
         b.across = 1; b.down = 1; b.predictor = 2; b.block_rows = a.block_rows;
         const unsigned long long groups = ((unsigned long long)b.block_rows + 3) / 4;
@@ -424,7 +419,7 @@ int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, 
         hipLaunchKernelGGL(dswx_untile_v1<unsigned char>, dim3((unsigned)groups), dim3(256), 0, s, b);
         HIP_TRY(hipGetLastError());
         Fp3Args g = {};
-        g.acc = static_cast<const unsigned char*>(ctx->untile_tmp); g.dst = static_cast<unsigned*>(plane);
+        g.acc = static_cast<const unsigned char*>(tmp.p); g.dst = static_cast<unsigned*>(plane);
         g.height = (int)height; g.width = (int)width; g.bw = block_width; g.bh = block_height; g.across = a.across;
         hipLaunchKernelGGL(dswx_untile_fp3_gather, dim3((unsigned)((width + 255) / 256), (unsigned)height), dim3(256), 0, s, g);
         HIP_TRY(hipGetLastError());
