@@ -469,7 +469,10 @@ int dswx_batch_place_slide(dswx_batch_t* batch, const dswx_params_t* params, uin
  * scale * (float32(band) - offset) with NaN on invalid pixels (_save_output_rgb_file, dswx_hls.py:3013-3036).
  * Compression stays on the host (include/dswx_codec.h); the byte shuffling between an inflated block and the
  * classifier's planes, and between its layers and the blocks to deflate, runs on the device with these entries.
- * All pointers are DEVICE pointers; asynchronous on `stream` (NULL = the context's stream). */
+ * All pointers are DEVICE pointers; asynchronous on `stream` (NULL = the context's stream).  Every plane and index array is
+ * aligned to its samples (any such address: no larger alignment is asked for), `blocks` of dswx_cog_blocks_device to 16
+ * bytes; a pointer that is not is refused with DSWX_ERR_ALIGN before anything is launched (dswx_copy_2d_device moves
+ * bytes and takes any address). */
 #define DSWX_COG_MAX_LEVELS 8
 typedef struct dswx_cog_layout {
     int32_t n_levels;                                /* the full-resolution image + the overview levels */

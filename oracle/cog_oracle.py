@@ -146,7 +146,8 @@ def rgb_planes(bands, diag, scales, offsets, clip=True):
     for b, sc, of in zip(bands, scales, offsets):
         if clip:
             b = np.clip(b, 1, None)
-        v = sc * (np.asarray(b, dtype=np.float32) - of)
+        with np.errstate(over='ignore'):
+            v = sc * (np.asarray(b, dtype=np.float32) - of)
         v = np.asarray(v, dtype=np.float32)
         if diag is not None:
             v[diag == 65535] = np.nan
@@ -250,3 +251,58 @@ def resample_nearest(arr, out_height, out_width):
         for j in range(out_width):
             out[i, j] = arr[y, min(int((j + 0.5) * w / out_width), w - 1)]
     return out
+
+
+def convolve_line_generic(line, first, weights):
+    """One line (Python floats, any stride already resolved) through one pass of the overview convolution with GIVEN taps:
+    output j = sum over k of line[clamp(first[j] + k, 0, n_in - 1)] * weights[j][k], normalised over the taps whose sample
+    is not NaN; a tap of zero weight contributes nothing (an infinite sample under it stays out); NaN when no weight is
+    left.  Python floats, tap order.  This is the contract of dswx_convolve_axis_device, element by element."""
+    n_in = len(line)
+    out = []
+    for f0, ws in zip(first, weights):
+        num = den = 0.0
+        for k, w in enumerate(ws):
+            v = line[min(max(int(f0) + k, 0), n_in - 1)]
+            if v != v:
+                continue
+            w = float(w)
+            if w > 0.0:
+                num += v * w
+            den += w
+        out.append(num / den if den > 0.0 else float('nan'))
+    return out
+
+
+def convolve_axis(lines, first, weights):
+    """convolve_line_generic on every line of float64 [n_lines, n_in] at once (whole-array operations, still tap by tap in
+    tap order) -> float64 [n_lines, n_out].  tests/test_raster_domain.py pins it against the element-wise form."""
+    with np.errstate(invalid='ignore'):             # (a signalling NaN raises the flag when it is widened)
+        lines = np.asarray(lines, dtype=np.float64)
+    first = np.asarray(first, dtype=np.int64)
+    weights = np.asarray(weights, dtype=np.float64)
+    n_in = lines.shape[1]
+    num = np.zeros((lines.shape[0], first.size))
+    den = np.zeros_like(num)
+    with np.errstate(all='ignore'):
+        for k in range(weights.shape[1]):
+            v = lines[:, np.clip(first + k, 0, n_in - 1)]
+            w = np.where(v != v, 0.0, weights[None, :, k])
+            num = num + np.where(w > 0.0, v, 0.0) * w
+            den = den + w
+        return np.where(den > 0.0, num / den, np.nan)
+
+
+def gdal_byte_vec(arr):
+    """gdal_byte on a whole floating-point or integer array at once (tests/test_raster_domain.py pins it against the
+    element-wise form on the rounding edges and on every exponent)."""
+    a = np.asarray(arr)
+    if a.dtype.kind != 'f':
+        v = a.astype(np.int64)
+        return np.where(v < 0, 0, np.where(v > 255, 255, v)).astype(np.uint8)
+    with np.errstate(invalid='ignore'):             # (a signalling NaN raises the flag when it is widened)
+        x = a.astype(np.float64)
+    x = np.where(x != x, 0.0, x)
+    x = np.where(x < 0.0, 0.0, np.where(x > 255.0, 255.0, x))
+    r = np.floor(x + 0.5)
+    return np.where(r > 255.0, 255.0, r).astype(np.uint8)

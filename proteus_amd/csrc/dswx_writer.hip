@@ -451,6 +451,8 @@ int dswx_rgb_planes_device(dswx_ctx_t* ctx, const int16_t* red, const int16_t* g
                            float* out, void* stream) {
     if (!ctx || !red || !green || !blue || !scale || !offset || !out) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (n_pixels < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
+    if (!aligned_to(red, 2) || !aligned_to(green, 2) || !aligned_to(blue, 2) || !aligned_to(diag, 2) || !aligned_to(out, 4))
+        return dswx_fail(DSWX_ERR_ALIGN, "planes must be aligned to their samples");
     if (n_pixels == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -471,6 +473,8 @@ int dswx_gather_2d_device(dswx_ctx_t* ctx, const void* src, int32_t elem_bytes, 
     if (src_height < 1 || src_width < 1 || n_rows < 0 || n_cols < 0 || n_rows > 65535)
         return dswx_fail(DSWX_ERR_ARG, "bad size (at most 65535 output rows)");
     if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4) return dswx_fail(DSWX_ERR_ARG, "elem_bytes must be 1, 2 or 4");
+    if (!aligned_to(src, (size_t)elem_bytes) || !aligned_to(dst, (size_t)elem_bytes) || !aligned_to(rows, 4) || !aligned_to(cols, 4))
+        return dswx_fail(DSWX_ERR_ALIGN, "planes must be aligned to their samples, the index arrays to 4 bytes");
     if (n_rows == 0 || n_cols == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -488,6 +492,7 @@ int dswx_gather_2d_device(dswx_ctx_t* ctx, const void* src, int32_t elem_bytes, 
 int dswx_to_byte_device(dswx_ctx_t* ctx, const void* src, int32_t src_kind, int64_t n, uint8_t* dst, void* stream) {
     if (!ctx || !src || !dst) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (n < 0 || src_kind < 1 || src_kind > 3) return dswx_fail(DSWX_ERR_ARG, "src_kind: 1 uint16, 2 int16, 3 float32");
+    if (!aligned_to(src, src_kind == 3 ? 4 : 2)) return dswx_fail(DSWX_ERR_ALIGN, "the plane must be aligned to its samples");
     if (n == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
@@ -507,6 +512,8 @@ int dswx_convolve_axis_device(dswx_ctx_t* ctx, const void* src, int32_t src_is_f
                               int64_t dst_elem_stride, void* stream) {
     if (!ctx || !src || !dst || !first || !weights) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (n_lines < 0 || n_in < 1 || n_out < 0 || taps < 1 || taps > 4096) return dswx_fail(DSWX_ERR_ARG, "bad size");
+    if (!aligned_to(src, src_is_f64 ? 8 : 4) || !aligned_to(dst, dst_is_f64 ? 8 : 4) || !aligned_to(first, 4) || !aligned_to(weights, 8))
+        return dswx_fail(DSWX_ERR_ALIGN, "src / dst must be aligned to their samples, first to 4 bytes, weights to 8");
     if (n_lines == 0 || n_out == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
