@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define DSWX_ABI_VERSION 6
+#define DSWX_ABI_VERSION 7
 
 enum {
     DSWX_OK = 0,
@@ -539,6 +539,49 @@ int dswx_to_byte_device(dswx_ctx_t* ctx, const void* src, int32_t src_kind, int6
 int dswx_gather_2d_device(dswx_ctx_t* ctx, const void* src, int32_t elem_bytes, int64_t src_height, int64_t src_width,
                           const int32_t* rows, int32_t n_rows, const int32_t* cols, int32_t n_cols, void* dst, void* stream);
 
+/* ---- checksums: what a plane contains, one 64-bit word per tile (ABI v7) ------------------------------------------
+ * A resident batch holds tens of gigabytes of layers in HBM; these entries say what is in them without the planes
+ * crossing PCIe: compare a resident tile with a file, a host array, an earlier run or another rank's copy by comparing
+ * eight bytes.  THE DEFINITION (independent of address, alignment, tile stride, launch geometry and device) -- for one
+ * tile of n elements of b bytes (b = 1, 2, 4 or 8):
+ *   take the n b bytes of the tile in memory order and split them into m = ceil(n b / 8) little-endian 64-bit words
+ *   w_0 .. w_(m-1); word 0 starts at element 0 of the tile whatever its address, the last word is zero-padded;
+ *       C = mix(n b) + sum over g of mix(w_g + (g + 1) K)        (mod 2^64)
+ *   K = DSWX_CHECKSUM_K (odd), and mix is the splitmix64 finaliser
+ *       x ^= x >> 30;  x *= DSWX_CHECKSUM_M1;  x ^= x >> 27;  x *= DSWX_CHECKSUM_M2;  x ^= x >> 31      (mod 2^64)
+ *   n = 0 is legal: C = mix(0) = 0.
+ * Properties (tests/test_checksum.py):
+ *   - the sum is commutative: any order of blocks and of their atomic adds gives the same value -- the device entries are
+ *     deterministic;
+ *   - mix is a bijection of the 64-bit words (xor-shifts and odd multiplies are): a change confined to ONE 8-byte word
+ *     ALWAYS changes C;
+ *   - the position key sits INSIDE the non-linear mix: transposed, shifted or row-swapped data is not cancelled linearly
+ *     (a linear form sum of w_g odd(g) misses a swap of the top bytes of two words 128 apart).
+ * Changes that touch several words are detected with probability 1 - 2^-64 under the usual heuristic; this is an
+ * integrity check against mistakes, not a cryptographic hash. */
+#define DSWX_CHECKSUM_K 0x9E3779B97F4A7C15ULL
+#define DSWX_CHECKSUM_M1 0xBF58476D1CE4E5B9ULL
+#define DSWX_CHECKSUM_M2 0x94D049BB133111EBULL
+/* One plane [n_tiles][tile_stride_elems] of elem_bytes-wide elements in DEVICE memory -> out[n_tiles] (device uint64: the
+ * checksum of the first n_elems elements of every tile; the bytes between n_elems and the stride are not read).
+ * Asynchronous on `stream` (NULL = the context's stream), no synchronisation inside: out is zeroed on the stream, then one
+ * kernel adds into it.  tile_stride_elems 0 = n_elems.  `plane` off its element alignment (or `out` off 8 bytes):
+ * DSWX_ERR_ALIGN, as the raster-format entries; elem_bytes not 1 / 2 / 4 / 8, a negative size or tile count, a stride below
+ * n_elems, or a NULL pointer with n_tiles > 0: DSWX_ERR_ARG.  (The arguments are checked before the context is.) */
+int dswx_checksum_device(dswx_ctx_t* ctx, const void* plane, int32_t elem_bytes, int64_t n_tiles, int64_t n_elems,
+                         int64_t tile_stride_elems, uint64_t* out_device_u64, void* stream);
+/* The planes of a resident batch selected by `plane_mask` (bit k = plane DSWX_PLANE_k: inputs, layers, extra layers, and
+ * DSWX_PLANE_COUNTERS as [n_tiles][3] int64), tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the
+ * last), the height x width pixels of every tile -> out[popcount(plane_mask)][n_tiles] in HOST memory, planes in ascending
+ * index order, complete on return.  ONE kernel launch for all selected planes, on `stream`; the addresses are those of
+ * dswx_batch_planes, so packed, separate-output and placed batches are alike.  A plane the batch does not have:
+ * DSWX_ERR_ARG, and dswx_last_error() names it.  (The device words live in an allocation made and freed by the call.) */
+int dswx_batch_checksum(dswx_batch_t* batch, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, uint64_t* out_host_u64,
+                        void* stream);
+/* The same definition on a HOST buffer in plain scalar C++: needs no device and no context.  The other half of a
+ * comparison -- the expected value of a host array or a decoded file -- not a fallback of the two entries above. */
+int dswx_checksum_host(const void* data, size_t n_bytes, uint64_t* out_u64);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -566,7 +609,7 @@ int dswx_event_destroy(dswx_ctx_t* ctx, void* event);
 int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
-/* Name and launch geometry of the kernel the last dswx_classify_* call on this
+/* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* call on this
  * context selected (for profiles / DESIGN.md): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import build as _build
 
-DSWX_ABI_VERSION = 6
+DSWX_ABI_VERSION = 7
 OK, ERR_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_ALIGN = 0, -1, -2, -3, -4, -5
 ADJ_MODES = {'mask': 0, 'ignore': 1, 'cover': 2}
 BAND_NAMES = ('blue', 'green', 'red', 'nir', 'swir1', 'swir2')
@@ -36,7 +36,8 @@ EXPORTED_SYMBOLS = (
     'dswx_shadow_layer_batch', 'dswx_landcover_mask_batch',
     'dswx_cog_layout', 'dswx_cog_blocks_device', 'dswx_untile_device', 'dswx_rgb_planes_device', 'dswx_copy_2d_device', 'dswx_convolve_axis_device',
     'dswx_to_byte_device', 'dswx_gather_2d_device',
-    'dswx_memcpy_h2d_async', 'dswx_memcpy_d2h_async')
+    'dswx_memcpy_h2d_async', 'dswx_memcpy_d2h_async',
+    'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host')
 
 
 class DswxError(RuntimeError):
@@ -262,6 +263,9 @@ def load_library(path=None):
         'dswx_copy_2d_device': (ctypes.c_int, [vp, vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, vp]),
         'dswx_memcpy_h2d_async': (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp]),
         'dswx_memcpy_d2h_async': (ctypes.c_int, [vp, vp, vp, ctypes.c_size_t, vp]),
+        'dswx_checksum_device': (ctypes.c_int, [vp, vp, ctypes.c_int32, i64, i64, i64, vp, vp]),
+        'dswx_batch_checksum': (ctypes.c_int, [vp, ctypes.c_uint32, i64, i64, vp, vp]),
+        'dswx_checksum_host': (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -801,6 +805,13 @@ class Context:
                                             int(src_pitch), int(width_bytes), int(height),
                                             ctypes.c_void_p(stream) if stream else None))
 
+    def checksum_device(self, plane_ptr, elem_bytes, n_tiles, n_elems, out_ptr, tile_stride=0, stream=None):
+        """dswx_checksum_device: the per-tile checksums (include/dswx_hip.h "checksums"; proteus_amd/checksum.py states the
+        definition in numpy) of one device plane [n_tiles][tile_stride] -> device uint64 [n_tiles] at out_ptr; asynchronous."""
+        _check(self.lib.dswx_checksum_device(self.handle, ctypes.c_void_p(plane_ptr), int(elem_bytes), int(n_tiles), int(n_elems),
+                                             int(tile_stride), ctypes.c_void_p(out_ptr),
+                                             ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -836,6 +847,16 @@ class Context:
         buf = ctypes.create_string_buffer(256)
         _check(self.lib.dswx_last_kernel_info(self.handle, buf, 256))
         return buf.value.decode()
+
+
+def checksum_host(data):
+    """dswx_checksum_host (no device needed): the checksum of a host buffer (bytes-like, or an array taken in C order)
+    by the library's scalar statement of the definition."""
+    a = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    v = ctypes.c_uint64()
+    _check(load_library().dswx_checksum_host(_host_ptr(a) if a.size else None, a.size, ctypes.byref(v)))
+    return int(v.value)
 
 
 def cog_layout(height, width, elem_bytes, factors=(), tile=512):
@@ -984,6 +1005,29 @@ class DeviceBatch:
         if not ptr:
             raise ValueError(f'plane {name!r} is not part of this batch (masks / extra_layers of DeviceBatch)')
         return ptr, dt
+
+    def plane_names(self):
+        """The planes this batch has (inputs, layers, extra layers), in the order of PLANE_INDEX."""
+        return [n for n in PLANE_INDEX if n != 'counters' and (
+            getattr(self.pout, n) if n == 'diag' or n in U8_LAYERS else
+            self.pin.band[BAND_NAMES.index(n)] if n in BAND_NAMES else getattr(self.pin, n))]
+
+    def checksums(self, names=None, tile0=0, n_tiles=None, stream=None):
+        """dswx_batch_checksum: {name: uint64 [n_tiles]}, the checksum of every selected plane of tiles tile0 .. tile0 +
+        n_tiles - 1 (default: every plane the batch has -- 'counters' only when named -- and every tile from tile0), by ONE
+        kernel launch; complete on return.  proteus_amd.checksum.checksum(read_tile(name, t)) is the same number."""
+        names = self.plane_names() if names is None else list(names)
+        mask = 0
+        for n in names:
+            if n not in PLANE_INDEX:
+                raise ValueError(f'unknown plane {n!r}')
+            mask |= 1 << PLANE_INDEX[n]
+        n_tiles = self.n_tiles - tile0 if n_tiles is None else n_tiles
+        order = sorted(set(names), key=PLANE_INDEX.get)
+        out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_checksum(self.handle, mask, int(tile0), int(n_tiles), _host_ptr(out),
+                                                ctypes.c_void_p(stream) if stream else None))
+        return {n: out[i] for i, n in enumerate(order)}
 
     def read_tile(self, name, tile):
         """Download one plane of one tile as [H,W]."""

@@ -301,6 +301,47 @@ int dswx_batch_synth(dswx_batch_t* b, uint64_t seed, int64_t tile0, void* stream
     return dswx_synth_batch(b->ctx, seed, tile0, &b->geom, &in, stream);
 }
 
+// Per-tile checksums of the selected planes (dswx_checksum.hip), one launch; the device words live in an allocation of
+// this call's own -- no scratch of the context, nothing to order against its other launches.
+int dswx_batch_checksum(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, uint64_t* out, void* stream) {
+    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
+    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
+    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
+        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
+                         (long long)n_tiles, (long long)b->geom.n_tiles);
+    dswx_checksum_plane planes[DSWX_BATCH_MAX_PLANES];
+    int n_planes = 0;
+    const uint64_t px = (uint64_t)b->geom.height * (uint64_t)b->geom.width, stride = (uint64_t)b->geom.tile_stride;
+    for (int k = 0; k < DSWX_BATCH_MAX_PLANES; ++k) {
+        if (!((plane_mask >> k) & 1u)) continue;
+        const bool counters = k == DSWX_PLANE_COUNTERS;
+        if (!b->ptr[k])
+            return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", k, counters ? "counters" : DSWX_PLANES[k].name);
+        const uint64_t eb = counters ? sizeof(int64_t) : DSWX_PLANES[k].bytes;
+        const uint64_t n = counters ? DSWX_N_COUNTERS : px, st = counters ? DSWX_N_COUNTERS : stride;
+        planes[n_planes++] = {(const char*)b->ptr[k] + (uint64_t)tile0 * st * eb, n * eb, st * eb};
+    }
+    if (n_planes == 0 || n_tiles == 0) return DSWX_OK;
+    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const size_t bytes = (size_t)n_planes * (size_t)n_tiles * sizeof(uint64_t);
+    uint64_t* dev = nullptr;
+    HIP_TRY(dswx_locked_malloc(&dev, bytes));
+    int rc = dswx_checksum_launch(ctx, planes, n_planes, n_tiles, dev, s);
+    if (rc == DSWX_OK) {
+        hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = dswx_fail(DSWX_ERR_HIP, "dswx_batch_checksum: reading the checksums failed: %s", hipGetErrorString(e));
+    } else {
+        (void)hipStreamSynchronize(s);         // whatever was queued must not outlive the allocation
+    }
+    (void)hipFree(dev);
+    return rc;
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

@@ -178,6 +178,15 @@ void dswx_lut_geometry(const dswx_ctx* ctx, long long groups, bool extras, int l
 int dswx_lut_launch(dswx_ctx* ctx, const KArgs& args, bool masks, dim3 grid, dim3 block, hipStream_t stream,
                     char* info, size_t info_len);
 
+// ---- checksums (dswx_checksum.hip): one plane of a launch, in bytes (the kernel does not know element sizes)
+struct dswx_checksum_plane {
+    const void* base;
+    uint64_t tile_bytes;      // checksummed bytes of every tile, from its start
+    uint64_t stride_bytes;    // between tiles
+};
+int dswx_checksum_launch(dswx_ctx* ctx, const dswx_checksum_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
+                         hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

@@ -43,6 +43,21 @@ class DevicePlane:
             self._host = self.engine.download(self)
         return self._host
 
+    def checksum(self):
+        """The checksum of the raster as it lies in HBM (dswx_checksum_device; proteus_amd.checksum.checksum of the same
+        array is the same number): eight bytes cross PCIe, not the raster.  A convenience -- nothing in the product run
+        calls it."""
+        if self.dtype.itemsize not in (1, 2, 4, 8):
+            raise ValueError(f'no checksum for {self.dtype} planes')
+        out = self.engine._take(8)
+        try:
+            with self.engine.lock, stages.span('gpu: checksum'):
+                self.engine.ctx.checksum_device(self.ptr, self.dtype.itemsize, 1, self.nbytes // self.dtype.itemsize, out.ptr)
+                self.engine.ctx.synchronize()
+                return int(out.download(np.uint64, 1)[0])
+        finally:
+            self.engine._give(out)
+
     def release(self):
         if self.buf is not None:
             self.engine._give(self.buf)
