@@ -250,11 +250,30 @@ def apply_landcover_and_shadow_masks(wtr_1, nir, landcover, shadow, thr):
 # ---------------------------------------------------------------------------
 # A11  _add_snow_to_cloud_layer :1996-2086  ('cover' branch :2055-2078)
 # ---------------------------------------------------------------------------
-def add_snow_to_cloud_layer(wtr_2, cloud, fmask, mask_adjacent_to_cloud_mode):
-    """In place on `cloud`; returns it."""
+def masked_dilation_by_shifts(seed, iterations=1, mask=None):
+    """A second, independent statement of scipy.ndimage.binary_dilation(seed, iterations=..., mask=...) with its
+    default structure (the 4-neighbour cross) and border value (False): synchronous iterations on shifted copies.  In
+    every iteration a cell inside `mask` becomes True when it or one of its four neighbours was True before the
+    iteration; cells outside the mask keep their value; nothing enters from outside the raster."""
+    x = np.array(seed, dtype=bool)
+    m = np.ones(x.shape, bool) if mask is None else np.asarray(mask, dtype=bool)
+    for _ in range(iterations):
+        near = x.copy()
+        near[1:, :] |= x[:-1, :]
+        near[:-1, :] |= x[1:, :]
+        near[:, 1:] |= x[:, :-1]
+        near[:, :-1] |= x[:, 1:]
+        x = x | (near & m)
+    return x
+
+
+def add_snow_to_cloud_layer(wtr_2, cloud, fmask, mask_adjacent_to_cloud_mode, binary_dilation=None):
+    """In place on `cloud`; returns it.  binary_dilation: the dilation to use in 'cover' mode (default: scipy's, as
+    the reference; masked_dilation_by_shifts is the second statement)."""
     snow = np.bitwise_and(fmask, 16) == 16
     if mask_adjacent_to_cloud_mode == 'cover':
-        from scipy.ndimage import binary_dilation
+        if binary_dilation is None:
+            from scipy.ndimage import binary_dilation
         adjacent = np.bitwise_and(fmask, 4) == 4
         grow_area = adjacent & (cloud == 0)
         snow = binary_dilation(snow, iterations=10, mask=grow_area)
@@ -321,7 +340,7 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
                   clip_negative_reflectance=True,
                   mask_adjacent_to_cloud_mode='mask',
                   apply_aerosol=True, aerosol_fmask_values=None,
-                  collapse=True, with_indices=False, offset_and_scale=None):
+                  collapse=True, with_indices=False, offset_and_scale=None, binary_dilation=None):
     """Run the whole per-pixel chain on one tile, in the reference's order.
 
     `bands` are the RAW int16 planes as read from file (fill values still in
@@ -329,7 +348,7 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
     when `collapse` is True (WTR, WTR-1, WTR-2 collapsed at save time,
     :2688-2689), or in the in-memory uncollapsed form otherwise, plus
     `WTR-1-AEROSOL` (the in-place remapped WTR-1 that feeds WTR-2, and that the
-    multi-band output file receives, :5381-5396) and `counters`.
+    multi-band output file receives, :5381-5396) and `counters`.  `binary_dilation`: see add_snow_to_cloud_layer.
     """
     if thr is None:
         thr = Thresholds()
@@ -355,7 +374,7 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
     wtr_2 = apply_landcover_and_shadow_masks(wtr_1, nir, landcover, shadow,
                                              thr)                  # :5268
     cloud = add_snow_to_cloud_layer(wtr_2, cloud, fmask,
-                                    mask_adjacent_to_cloud_mode)   # :5282
+                                    mask_adjacent_to_cloud_mode, binary_dilation)   # :5282
     wtr = apply_cloud_masking(wtr_2, cloud)                        # :5286
     bwtr = get_binary_water_layer(wtr)                             # :5358
     conf = get_confidence_layer(wtr_2, cloud)                      # :5368

@@ -23,6 +23,7 @@ sys.path.insert(0, ROOT)
 from oracle._ref_import import import_reference  # noqa: E402
 from proteus_amd.synth import synth_tile          # noqa: E402
 from oracle import band_inputs                     # noqa: E402
+from oracle import cover_inputs                    # noqa: E402
 
 # DSWX_GOLDEN_OUT: write somewhere else (tests/test_oracle_golden.py::test_goldens_reproduce_from_reference regenerates
 # into a temporary directory and compares with the committed fixtures)
@@ -382,6 +383,15 @@ TILE_CASES = [
                 (3.0, 16384.0)]),
     dict(name='t64_band_f32_neg_zero_scale', tile=37, H=64, W=64, land=1, shad=1, bands='int16', thr='reflectance',
          scale=[(-1e-4, 0.0), (0.0, 7.0), (1e-4, -30.5), (-2.75e-5, 1000.0), (0.0, 0.0), (1e-4, 16384.0)]),
+    # the named 'cover' domains (oracle/cover_inputs.py) through the reference's own _add_snow_to_cloud_layer, aimed at the
+    # window seams of both stage-2 kernels (rows 222; columns 222 and 94): the 17-pixel dependency with the far seed either
+    # way, walled corridors that the snow front walks for all ten iterations, all 256 Fmask bytes in patches, diamonds cut
+    # by fill, ocean and shadow
+    dict(name='t260x300_cover_chain17', tile=38, H=260, W=300, mode='cover', scene='chain17'),
+    dict(name='t260x300_cover_chain17_toggled', tile=39, H=260, W=300, mode='cover', scene='chain17_toggled'),
+    dict(name='t260x300_cover_walled_corridors', tile=40, H=260, W=300, mode='cover', scene='corridors'),
+    dict(name='t160x112_cover_bytes256', tile=41, H=160, W=112, mode='cover', scene='bytes256'),
+    dict(name='t240x112_cover_holes', tile=42, H=240, W=112, mode='cover', scene='holes'),
 ]
 
 
@@ -512,6 +522,9 @@ def gen_tiles(ref):
         land = s['land'] if case.get('land') else None
         shad = s['shad'].astype(bool) if case.get('shad') else None
         ocean = s['ocean'] if case.get('ocean') else None
+        if case.get('scene'):
+            bands, fmask, scene_masks = cover_inputs.planes(cover_inputs.scenes(case['scene'], H, W, nw=(8, 4))[0])
+            shad, ocean = scene_masks.get('shad'), scene_masks.get('ocean')
         if case.get('domains'):
             drng = np.random.default_rng(3000 + case['tile'])     # (its own stream, as the fills above)
             dom = case['domains']
