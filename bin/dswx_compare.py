@@ -11,8 +11,10 @@ from proteus_amd.dswx_hls import compare_dswx_hls_products   # noqa: E402
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Compare two DSWx-HLS products')
     ap.add_argument('input_file', type=str, nargs=2, help='Input images')
+    ap.add_argument('--device', type=int, default=None, metavar='N',
+                    help='compare the bands on GPU N: both files are read into resident planes and only the records cross PCIe')
     args = ap.parse_args(argv)
-    return 0 if compare_dswx_hls_products(args.input_file[0], args.input_file[1]) else 1
+    return 0 if compare_dswx_hls_products(args.input_file[0], args.input_file[1], device=args.device) else 1
 
 
 if __name__ == '__main__':

@@ -582,6 +582,59 @@ int dswx_batch_checksum(dswx_batch_t* batch, uint32_t plane_mask, int64_t tile0,
  * comparison -- the expected value of a host array or a decoded file -- not a fallback of the two entries above. */
 int dswx_checksum_host(const void* data, size_t n_bytes, uint64_t* out_u64);
 
+/* ---- compare: where two planes differ, in how many elements and by how much (additive to ABI v7) ---------------------
+ * A checksum says THAT a resident tile differs; these entries say where, in how many elements and by how much, again
+ * without a plane crossing PCIe: 32 bytes per tile come back.  A C caller tests for them with DSWX_HAS_COMPARE.
+ * THE DEFINITION.  Two planes a, b of the same element kind (DSWX_CMP_*), each [n_tiles][tile_stride] with its OWN stride
+ * and address; only the first n_elems elements of a tile are read, the padding up to the stride never is.  An element pair
+ * (x, y) = (a[i], b[i]) is CLOSE when numpy's isclose(a, b, rtol, atol, equal_nan) says so -- operation by operation:
+ *   integer kinds   |x - y| <= atol + rtol |y| evaluated in double (both values convert exactly);
+ *   DSWX_CMP_F64    the same test in double;
+ *   DSWX_CMP_F32    all in float32, as numpy evaluates it for float32 arrays against Python-float tolerances: atol and rtol
+ *                   are rounded to float32 first, d = |x - y| is ONE float32 subtraction, tol = atol32 + rtol32 |y| a float32
+ *                   multiply, then a float32 add (no contraction into a fused multiply-add); close iff d <= tol and y is finite;
+ *   float kinds, in addition: x == y is close (equal infinities, -0 against +0), and a pair of NaNs is close iff equal_nan.
+ *   rtol = atol = 0 is value equality.
+ * Per tile the result is one record:
+ *   n_diff        the number of pairs that are not close;
+ *   first         the smallest flat element index within the tile that is not close, -1 if there is none;
+ *   max_abs_diff  the maximum of |double(x) - double(y)| over the not-close pairs in which neither value is NaN: 0.0 when
+ *                 there is no such pair, +inf when an infinity is involved;
+ *   reserved      zero.
+ * The three are a sum, a minimum and a maximum of non-negative doubles (which are ordered as their bit patterns): all
+ * order-independent, so the device entries are deterministic whatever the order of the blocks and of their atomics. */
+#define DSWX_HAS_COMPARE 1
+enum { DSWX_CMP_U8 = 0, DSWX_CMP_U16 = 1, DSWX_CMP_I16 = 2, DSWX_CMP_F32 = 3, DSWX_CMP_F64 = 4, DSWX_CMP_KINDS = 5 };
+typedef struct dswx_compare {
+    int64_t n_diff;
+    int64_t first;
+    double max_abs_diff;
+    uint64_t reserved;
+} dswx_compare_t;
+/* Two planes in DEVICE memory -> out[n_tiles] (device records).  Asynchronous on `stream` (NULL = the context's stream), no
+ * synchronisation inside: the records are initialised on the stream, then one kernel fills them.  A stride of 0 = n_elems;
+ * a == b is legal.  `kind` not a DSWX_CMP_* value, a negative size or tile count, a stride below n_elems, a NULL pointer
+ * with n_tiles > 0, atol or rtol negative or not finite: DSWX_ERR_ARG; a plane off its element alignment, or `out` off 8
+ * bytes: DSWX_ERR_ALIGN.  (The arguments are checked before the context is.) */
+int dswx_compare_device(dswx_ctx_t* ctx, const void* a, const void* b, int32_t kind, int64_t n_tiles, int64_t n_elems,
+                        int64_t a_stride_elems, int64_t b_stride_elems, double atol, double rtol, int32_t equal_nan,
+                        dswx_compare_t* out_device_records, void* stream);
+/* The planes selected by `plane_mask` (bit k = plane DSWX_PLANE_k: inputs, layers, extra layers) of TWO resident batches,
+ * tiles tile0 .. tile0 + n_tiles - 1 of both (n_tiles DSWX_BATCH_ALL_TILES = up to the last tile of batch_a), the height x
+ * width pixels of every tile -> out[popcount(plane_mask)][n_tiles] records in HOST memory, planes in ascending index order,
+ * complete on return.  ONE kernel launch for all selected planes, on `stream` (NULL = the stream of batch_a's context); the
+ * kinds come from the library's plane table (bands int16, DIAG uint16, the rest uint8), the addresses are those of
+ * dswx_batch_planes, so packed, separate-output, placed, padded and contiguous batches mix freely.  The batches must be on
+ * the same device and have equal height and width (their strides may differ): otherwise DSWX_ERR_ARG.  A plane that either
+ * batch lacks: DSWX_ERR_ARG, and dswx_last_error() names it.  DSWX_PLANE_COUNTERS in the mask: DSWX_ERR_ARG (twenty-four
+ * bytes per tile: compare their checksums, or the counters themselves).  batch_a == batch_b is legal. */
+int dswx_batch_compare(dswx_batch_t* batch_a, dswx_batch_t* batch_b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles,
+                       double atol, double rtol, int32_t equal_nan, dswx_compare_t* out_host_records, void* stream);
+/* The same definition on two HOST buffers in plain scalar C++: needs no device and no context.  The other half of a
+ * comparison -- what the record of a host array against a decoded file is -- not a fallback of the two entries above. */
+int dswx_compare_host(const void* a, const void* b, int32_t kind, int64_t n_elems, double atol, double rtol,
+                      int32_t equal_nan, dswx_compare_t* out_record);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);

@@ -37,7 +37,10 @@ EXPORTED_SYMBOLS = (
     'dswx_cog_layout', 'dswx_cog_blocks_device', 'dswx_untile_device', 'dswx_rgb_planes_device', 'dswx_copy_2d_device', 'dswx_convolve_axis_device',
     'dswx_to_byte_device', 'dswx_gather_2d_device',
     'dswx_memcpy_h2d_async', 'dswx_memcpy_d2h_async',
-    'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host')
+    'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host',
+    'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host')
+HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
+CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 
 
 class DswxError(RuntimeError):
@@ -105,6 +108,12 @@ class BatchInfo(ctypes.Structure):
                 ('kept_launch_ms', ctypes.c_float), ('va_reserved_bytes', ctypes.c_uint64),
                 ('va_retired_bytes', ctypes.c_uint64), ('va_budget_bytes', ctypes.c_uint64),
                 ('va_pooled_bytes', ctypes.c_uint64), ('note', ctypes.c_char * 256)]
+
+
+class CompareRecord(ctypes.Structure):
+    """dswx_compare_t; proteus_amd.compare.RECORD is the same layout as a numpy dtype."""
+    _fields_ = [('n_diff', ctypes.c_int64), ('first', ctypes.c_int64), ('max_abs_diff', ctypes.c_double),
+                ('reserved', ctypes.c_uint64)]
 
 
 COG_MAX_LEVELS = 8
@@ -266,6 +275,11 @@ def load_library(path=None):
         'dswx_checksum_device': (ctypes.c_int, [vp, vp, ctypes.c_int32, i64, i64, i64, vp, vp]),
         'dswx_batch_checksum': (ctypes.c_int, [vp, ctypes.c_uint32, i64, i64, vp, vp]),
         'dswx_checksum_host': (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]),
+        'dswx_compare_device': (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, i64, i64, i64, i64, ctypes.c_double, ctypes.c_double,
+                                               ctypes.c_int32, vp, vp]),
+        'dswx_batch_compare': (ctypes.c_int, [vp, vp, ctypes.c_uint32, i64, i64, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_int32, vp, vp]),
+        'dswx_compare_host': (ctypes.c_int, [vp, vp, ctypes.c_int32, i64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -812,6 +826,16 @@ class Context:
                                              int(tile_stride), ctypes.c_void_p(out_ptr),
                                              ctypes.c_void_p(stream) if stream else None))
 
+    def compare_device(self, a_ptr, b_ptr, kind, n_tiles, n_elems, out_ptr, a_stride=0, b_stride=0, atol=0.0, rtol=0.0,
+                       equal_nan=True, stream=None):
+        """dswx_compare_device: two device planes [n_tiles][stride] of one kind (CMP_*; include/dswx_hip.h "compare",
+        proteus_amd/compare.py states the definition in numpy) -> device records [n_tiles] (compare.RECORD) at out_ptr;
+        asynchronous."""
+        _check(self.lib.dswx_compare_device(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), int(kind), int(n_tiles),
+                                            int(n_elems), int(a_stride), int(b_stride), float(atol), float(rtol),
+                                            int(bool(equal_nan)), ctypes.c_void_p(out_ptr),
+                                            ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -857,6 +881,19 @@ def checksum_host(data):
     v = ctypes.c_uint64()
     _check(load_library().dswx_checksum_host(_host_ptr(a) if a.size else None, a.size, ctypes.byref(v)))
     return int(v.value)
+
+
+def compare_host(a, b, atol=0.0, rtol=0.0, equal_nan=True):
+    """dswx_compare_host (no device needed): the record (compare.RECORD scalar) of two host arrays of one kind and size,
+    taken in C order, by the library's scalar statement of the definition."""
+    from .compare import RECORD, kind_of
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.dtype != b.dtype or a.size != b.size:
+        raise ValueError(f'{a.dtype} x {a.size} against {b.dtype} x {b.size}')
+    rec = np.zeros(1, dtype=RECORD)
+    _check(load_library().dswx_compare_host(_host_ptr(a) if a.size else None, _host_ptr(b) if b.size else None, kind_of(a.dtype),
+                                            a.size, float(atol), float(rtol), int(bool(equal_nan)), _host_ptr(rec)))
+    return rec[0]
 
 
 def cog_layout(height, width, elem_bytes, factors=(), tile=512):
@@ -1027,6 +1064,24 @@ class DeviceBatch:
         out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=np.uint64)
         _check(self.ctx.lib.dswx_batch_checksum(self.handle, mask, int(tile0), int(n_tiles), _host_ptr(out),
                                                 ctypes.c_void_p(stream) if stream else None))
+        return {n: out[i] for i, n in enumerate(order)}
+
+    def compare(self, other, names=None, tile0=0, n_tiles=None, atol=0.0, rtol=0.0, equal_nan=True, stream=None):
+        """dswx_batch_compare: {name: compare.RECORD [n_tiles]}, this batch's selected planes against `other`'s (default:
+        every plane this batch has), tiles tile0 .. tile0 + n_tiles - 1 of both, by ONE kernel launch; complete on return.
+        proteus_amd.compare.compare(self.read_tile(name, t), other.read_tile(name, t), ...) is the same record."""
+        from .compare import RECORD
+        names = self.plane_names() if names is None else list(names)
+        mask = 0
+        for n in names:
+            if n not in PLANE_INDEX:
+                raise ValueError(f'unknown plane {n!r}')
+            mask |= 1 << PLANE_INDEX[n]
+        n_tiles = self.n_tiles - tile0 if n_tiles is None else n_tiles
+        order = sorted(set(names), key=PLANE_INDEX.get)
+        out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=RECORD)
+        _check(self.ctx.lib.dswx_batch_compare(self.handle, other.handle, mask, int(tile0), int(n_tiles), float(atol), float(rtol),
+                                               int(bool(equal_nan)), _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
         return {n: out[i] for i, n in enumerate(order)}
 
     def read_tile(self, name, tile):

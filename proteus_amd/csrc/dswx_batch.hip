@@ -342,6 +342,57 @@ int dswx_batch_checksum(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int
     return rc;
 }
 
+// The selected planes of two resident batches compared pair by pair (dswx_compare.hip), one launch; like the checksums the
+// device records live in an allocation of this call's own.
+int dswx_batch_compare(dswx_batch_t* a, dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, double atol,
+                       double rtol, int32_t equal_nan, dswx_compare_t* out, void* stream) {
+    if (!a || !b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
+    if ((plane_mask >> DSWX_PLANE_COUNTERS) & 1u)
+        return dswx_fail(DSWX_ERR_ARG, "the counters are not compared here (24 bytes per tile): compare their checksums instead "
+                         "(dswx_batch_checksum with DSWX_PLANE_COUNTERS)");
+    if (a->device != b->device) return dswx_fail(DSWX_ERR_ARG, "the batches are on different devices (%d and %d)", a->device, b->device);
+    if (a->geom.height != b->geom.height || a->geom.width != b->geom.width)
+        return dswx_fail(DSWX_ERR_ARG, "the batches differ in tile size: %lld x %lld against %lld x %lld", (long long)a->geom.height,
+                         (long long)a->geom.width, (long long)b->geom.height, (long long)b->geom.width);
+    if (int rc = dswx_compare_check_tol(atol, rtol)) return rc;
+    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= a->geom.n_tiles) n_tiles = a->geom.n_tiles - tile0;
+    for (const dswx_batch* x : {a, b})
+        if (tile0 < 0 || n_tiles < 0 || tile0 > x->geom.n_tiles || n_tiles > x->geom.n_tiles - tile0)
+            return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside a batch (%lld resident)", (long long)tile0, (long long)n_tiles,
+                             (long long)x->geom.n_tiles);
+    dswx_compare_pair pairs[DSWX_BATCH_MAX_PLANES];
+    int n_pairs = 0;
+    const uint64_t px = (uint64_t)a->geom.height * (uint64_t)a->geom.width;
+    for (int k = 0; k < DSWX_PLANE_COUNTERS; ++k) {
+        if (!((plane_mask >> k) & 1u)) continue;
+        const dswx_plane_desc& d = DSWX_PLANES[k];
+        if (!a->ptr[k] || !b->ptr[k])
+            return dswx_fail(DSWX_ERR_ARG, "batch %s has no plane %d (%s)", !a->ptr[k] ? (!b->ptr[k] ? "a (nor b)" : "a") : "b", k, d.name);
+        const uint64_t sa = (uint64_t)a->geom.tile_stride, sb = (uint64_t)b->geom.tile_stride;
+        pairs[n_pairs++] = {(const char*)a->ptr[k] + (uint64_t)tile0 * sa * d.bytes, (const char*)b->ptr[k] + (uint64_t)tile0 * sb * d.bytes,
+                            d.kind, px, sa, sb};
+    }
+    if (n_pairs == 0 || n_tiles == 0) return DSWX_OK;
+    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
+    dswx_ctx* ctx = a->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    const size_t bytes = (size_t)n_pairs * (size_t)n_tiles * sizeof(dswx_compare_t);
+    dswx_compare_t* dev = nullptr;
+    HIP_TRY(dswx_locked_malloc(&dev, bytes));
+    int rc = dswx_compare_launch(ctx, pairs, n_pairs, n_tiles, atol, rtol, equal_nan, dev, s);
+    if (rc == DSWX_OK) {
+        hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) rc = dswx_fail(DSWX_ERR_HIP, "dswx_batch_compare: reading the records failed: %s", hipGetErrorString(e));
+    } else {
+        (void)hipStreamSynchronize(s);         // whatever was queued must not outlive the allocation
+    }
+    (void)hipFree(dev);
+    return rc;
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

@@ -124,10 +124,12 @@ struct dswx_plane_desc {
     unsigned char bytes;      // per pixel
     signed char batch;        // DSWX_PLANE_* index; -1: not part of a batch (the float64 index planes)
     unsigned short offset;    // of the pointer inside its struct
+    signed char kind;         // DSWX_CMP_* of its pixels (dswx_batch_compare)
 };
-#define DSWX_BAND_(k) {"band[" #k "]", true, 2, DSWX_PLANE_BAND0 + k, offsetof(dswx_planes_in_t, band) + k * sizeof(void*)}
-#define DSWX_IN_(f, idx) {#f, true, 1, idx, offsetof(dswx_planes_in_t, f)}
-#define DSWX_OUT_(f, bytes, idx) {#f, false, bytes, idx, offsetof(dswx_planes_out_t, f)}
+#define DSWX_BAND_(k) {"band[" #k "]", true, 2, DSWX_PLANE_BAND0 + k, offsetof(dswx_planes_in_t, band) + k * sizeof(void*), DSWX_CMP_I16}
+#define DSWX_IN_(f, idx) {#f, true, 1, idx, offsetof(dswx_planes_in_t, f), DSWX_CMP_U8}
+#define DSWX_OUT_(f, bytes, idx) \
+    {#f, false, bytes, idx, offsetof(dswx_planes_out_t, f), bytes == 1 ? DSWX_CMP_U8 : bytes == 2 ? DSWX_CMP_U16 : DSWX_CMP_F64}
 constexpr dswx_plane_desc DSWX_PLANES[] = {
     DSWX_BAND_(0), DSWX_BAND_(1), DSWX_BAND_(2), DSWX_BAND_(3), DSWX_BAND_(4), DSWX_BAND_(5),
     DSWX_IN_(fmask, DSWX_PLANE_FMASK), DSWX_IN_(land, DSWX_PLANE_LAND), DSWX_IN_(shad, DSWX_PLANE_SHAD),
@@ -186,6 +188,19 @@ struct dswx_checksum_plane {
 };
 int dswx_checksum_launch(dswx_ctx* ctx, const dswx_checksum_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
                          hipStream_t s);
+
+// ---- compare (dswx_compare.hip): one plane pair of a launch, in elements of its kind
+struct dswx_compare_pair {
+    const void* a;
+    const void* b;
+    int kind;                 // DSWX_CMP_*
+    uint64_t n_elems;         // compared elements of every tile, from its start
+    uint64_t a_stride_elems, b_stride_elems;      // between tiles
+};
+int dswx_compare_elem_bytes(int kind);            // 0: not a kind
+int dswx_compare_check_tol(double atol, double rtol);
+int dswx_compare_launch(dswx_ctx* ctx, const dswx_compare_pair* pairs, int n_pairs, int64_t n_tiles, double atol, double rtol,
+                        int equal_nan, dswx_compare_t* out, hipStream_t s);
 
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,

@@ -1525,9 +1525,17 @@ def _compare_dswx_hls_metadata(metadata_1, metadata_2):
     return None, True
 
 
-def compare_dswx_hls_products(file_1, file_2):
+def compare_dswx_hls_products(file_1, file_2, device=None):
     """Band-wise np.allclose(atol=1e-6, equal_nan=True), identical geotransform, identical
-    metadata except LICENSE and the keys above (:710-784).  Prints an [OK]/[FAIL] report."""
+    metadata except LICENSE and the keys above (:710-784).  Prints an [OK]/[FAIL] report.
+
+    device=None: the bands are read into host arrays and compared with numpy, as the reference does.
+    device=N: both files are read through the engine of device N into resident planes and every band is compared there
+    (dswx_compare_device with atol=1e-6, rtol=1e-5, equal_nan=True: the values np.allclose uses); only the pair of values
+    at the first difference is fetched, by two element-sized copies.  Same report, with one known difference: for a NaN
+    against a number the host path prints no position (its `abs(diff) > tol` scan skips NaN), the device path prints the
+    first element that isclose rejects.  (Files of equal shape but different sample types are not compared on the device:
+    GeoTiffError.)"""
     for f in (file_1, file_2):
         if not os.path.isfile(f):
             print(f'ERROR file not found: {f}')
@@ -1535,8 +1543,13 @@ def compare_dswx_hls_products(file_1, file_2):
     print('Comparing files:')
     print(f'    file 1: {file_1}')
     print(f'    file 2: {file_2}')
-    a1, i1 = geotiff.read_geotiff(file_1)
-    a2, i2 = geotiff.read_geotiff(file_2)
+    if device is None:
+        a1, i1 = geotiff.read_geotiff(file_1)
+        a2, i2 = geotiff.read_geotiff(file_2)
+    else:
+        engine = pipeline.engine_of(get_context(device))
+        p1, i1 = engine.read_bands(file_1)
+        p2, i2 = engine.read_bands(file_2)
     all_ok = True
 
     def mark(flag):
@@ -1550,19 +1563,35 @@ def compare_dswx_hls_products(file_1, file_2):
         print(' ' * 7 + f'Input 1 has {i1.bands} bands and input 2 has {i2.bands} bands')
         return False
     print('Comparing DSWx bands...')
-    b1 = a1[None] if a1.ndim == 2 else a1
-    b2 = a2[None] if a2.ndim == 2 else a2
-    for b in range(i1.bands):
-        same = b1[b].shape == b2[b].shape and bool(np.allclose(
-            b1[b], b2[b], atol=COMPARE_DSWX_HLS_PRODUCTS_ERROR_TOLERANCE, equal_nan=True))
-        print(f'{mark(same)}     Band {b + 1} - {i1.descriptions[b]}"')
-        if not same and b1[b].shape == b2[b].shape:
-            bad = np.argwhere(np.abs(b1[b].astype(np.float64) - b2[b].astype(np.float64)) >
-                              COMPARE_DSWX_HLS_PRODUCTS_ERROR_TOLERANCE)
-            if bad.size:
-                y, x = bad[0]
-                print(' ' * 7 + f'     * input 1 has value "{b1[b][y, x]}" in position (x: {x},'
-                      f' y: {y}) whereas input 2 has value "{b2[b][y, x]}" in the same position.')
+    if device is None:
+        b1 = a1[None] if a1.ndim == 2 else a1
+        b2 = a2[None] if a2.ndim == 2 else a2
+        for b in range(i1.bands):
+            same = b1[b].shape == b2[b].shape and bool(np.allclose(
+                b1[b], b2[b], atol=COMPARE_DSWX_HLS_PRODUCTS_ERROR_TOLERANCE, equal_nan=True))
+            print(f'{mark(same)}     Band {b + 1} - {i1.descriptions[b]}"')
+            if not same and b1[b].shape == b2[b].shape:
+                bad = np.argwhere(np.abs(b1[b].astype(np.float64) - b2[b].astype(np.float64)) >
+                                  COMPARE_DSWX_HLS_PRODUCTS_ERROR_TOLERANCE)
+                if bad.size:
+                    y, x = bad[0]
+                    print(' ' * 7 + f'     * input 1 has value "{b1[b][y, x]}" in position (x: {x},'
+                          f' y: {y}) whereas input 2 has value "{b2[b][y, x]}" in the same position.')
+    else:
+        comparable = p1.shape == p2.shape and p1.dtype == p2.dtype
+        if not comparable and p1.shape == p2.shape:
+            raise geotiff.GeoTiffError(f'the device comparison needs one sample type: {p1.dtype} against {p2.dtype}')
+        rec = p1.compare(p2, atol=COMPARE_DSWX_HLS_PRODUCTS_ERROR_TOLERANCE, rtol=1e-5, equal_nan=True) if comparable else None
+        for b in range(i1.bands):
+            same = comparable and int(rec[b]['n_diff']) == 0
+            print(f'{mark(same)}     Band {b + 1} - {i1.descriptions[b]}"')
+            if not same and comparable:
+                at = b * i1.height * i1.width + int(rec[b]['first'])
+                y, x = divmod(int(rec[b]['first']), i1.width)
+                print(' ' * 7 + f'     * input 1 has value "{p1.element(at)}" in position (x: {x},'
+                      f' y: {y}) whereas input 2 has value "{p2.element(at)}" in the same position.')
+        p1.release()
+        p2.release()
     same = bool(np.array_equal(i1.geotransform, i2.geotransform))
     print(f'{mark(same)}Comparing geotransform')
     if not same:

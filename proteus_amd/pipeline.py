@@ -58,6 +58,29 @@ class DevicePlane:
         finally:
             self.engine._give(out)
 
+    def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
+        """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
+        proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
+        leading index of a [n, H, W] stack, else one for the raster; 32 bytes per record cross PCIe, not the rasters."""
+        from .compare import RECORD, kind_of
+        if self.shape != other.shape or self.dtype != other.dtype:
+            raise ValueError(f'{self.dtype} {self.shape} against {other.dtype} {other.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        n_elems = self.nbytes // self.dtype.itemsize // max(n_tiles, 1)
+        out = self.engine._take(32 * max(n_tiles, 1))
+        try:
+            with self.engine.lock, stages.span('gpu: compare'):
+                self.engine.ctx.compare_device(self.ptr, other.ptr, kind_of(self.dtype), n_tiles, n_elems, out.ptr,
+                                               atol=atol, rtol=rtol, equal_nan=equal_nan)
+                self.engine.ctx.synchronize()
+                return out.download(RECORD, n_tiles)
+        finally:
+            self.engine._give(out)
+
+    def element(self, index):
+        """One element of the raster (flat index, C order) by an element-sized copy."""
+        return self.buf.download(self.dtype, 1, int(index) * self.dtype.itemsize)[0]
+
     def release(self):
         if self.buf is not None:
             self.engine._give(self.buf)
@@ -179,6 +202,38 @@ class TileEngine:
             with self.lock, stages.span('gpu: blocks -> plane (h2d + untile)'):
                 self.ctx.h2d_async(dev_blocks.ptr, staging, need)
                 self.ctx.untile_device(dev_blocks.ptr, d.dt.itemsize, info.height, info.width, d.bw, d.bh, d.predictor, plane.ptr)
+                self.ctx.synchronize()
+        finally:
+            self._give(dev_blocks)
+        return plane, info
+
+    def read_bands(self, path):
+        """Every band of a GeoTIFF -> (DevicePlane [B, H, W], GeoTiffInfo): what compare_dswx_hls_products needs of a
+        product file.  Band-planar files (what write_geotiff writes) in a layout dswx_untile_device takes are inflated on host
+        threads and untiled band by band on the device; any other layout is untiled by the host reader (the same bytes) and
+        uploaded."""
+        d = geotiff.open_geotiff(path)
+        info = d.info
+        B, H, W = d.spp, info.height, info.width
+        probe_spp, d.spp = d.spp, 1                      # device_untile_ok judges the layout of ONE band
+        try:
+            ok = (B == 1 or d.planar == 2) and self.device_untile_ok(d)
+        finally:
+            d.spp = probe_spp
+        if not ok:
+            return self.upload(d.untile(d.inflate())), info
+        need = d.n_blocks * d.block_bytes
+        staging = self.ctx.pinned_empty((need,), np.uint8)
+        d.inflate(staging)
+        dev_blocks = self._take(need)
+        plane = self.plane((B, H, W), info.dtype)
+        per_band = need // B
+        try:
+            with self.lock, stages.span('gpu: blocks -> plane (h2d + untile)'):
+                self.ctx.h2d_async(dev_blocks.ptr, staging, need)
+                for b in range(B):
+                    self.ctx.untile_device(dev_blocks.ptr + b * per_band, d.dt.itemsize, H, W, d.bw, d.bh, d.predictor,
+                                           plane.ptr + b * H * W * d.dt.itemsize)
                 self.ctx.synchronize()
         finally:
             self._give(dev_blocks)
