@@ -68,7 +68,11 @@ def load():
         _lib.oracle_classify.restype = ctypes.c_int
         _lib.oracle_check_quotient_predicate.restype = ctypes.c_int64
         _lib.oracle_check_quotient_predicate.argtypes = [
-            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        _lib.oracle_check_quotient_pairs.restype = ctypes.c_int64
+        _lib.oracle_check_quotient_pairs.argtypes = [
+            ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     return _lib
 
@@ -108,9 +112,25 @@ def classify(params, bands, fmask, land=None, shad=None, ocean=None,
     return res
 
 
-def check_quotient_predicate(t, less_than, n_lo=-32768, n_hi=32768):
+BOTH_FORMS = 3      # bit 0: the compare form (quot_gt / quot_lt), bit 1: the sign-bit form (lut_group)
+
+
+def check_quotient_predicate(t, less_than, n_lo=-32768, n_hi=32768, forms=BOTH_FORMS):
+    """(mismatches, first (n, d)) of the device predicate's `forms` against fl64(n / d) > t (< t) over every int16 d and
+    n in [n_lo, n_hi)."""
     lib = load()
     bn, bd = ctypes.c_int(0), ctypes.c_int(0)
-    bad = lib.oracle_check_quotient_predicate(float(t), int(less_than), n_lo, n_hi,
+    bad = lib.oracle_check_quotient_predicate(float(t), int(less_than), int(forms), n_lo, n_hi,
                                               ctypes.byref(bn), ctypes.byref(bd))
+    return int(bad), (bn.value, bd.value)
+
+
+def check_quotient_pairs(t, less_than, n, d, forms=BOTH_FORMS):
+    """The same on the pairs (n[i], d[i])."""
+    lib = load()
+    n, d = np.ascontiguousarray(n, dtype=np.int16), np.ascontiguousarray(d, dtype=np.int16)
+    assert n.shape == d.shape
+    bn, bd = ctypes.c_int(0), ctypes.c_int(0)
+    bad = lib.oracle_check_quotient_pairs(float(t), int(less_than), int(forms), n.size, n.ctypes.data, d.ctypes.data,
+                                          ctypes.byref(bn), ctypes.byref(bd))
     return int(bad), (bn.value, bd.value)

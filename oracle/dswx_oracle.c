@@ -13,8 +13,9 @@
  * Function comments give the reference lines.
  *
  * Also here: oracle_check_quotient_predicate(), an exhaustive (all 2^32 int16
- * pairs) proof-by-enumeration that the kernel's FMA predicate equals the
- * reference's `fl64(n/d) > t` / `< t`.
+ * pairs) proof-by-enumeration that both forms of the kernels' FMA predicate equal
+ * the reference's `fl64(n/d) > t` / `< t`, and oracle_check_quotient_pairs(), the
+ * same on a list of pairs.
  */
 #include <math.h>
 #include <stdint.h>
@@ -212,38 +213,87 @@ int oracle_classify(const dswx_params_t* p, int64_t n, const dswx_planes_in_t* i
 }
 
 /*
- * Enumerates every (n, d) in int16 x int16 with n in [n_lo, n_hi) and counts the
- * pairs where the division-free predicate of the HIP kernel
+ * The division-free predicate of the HIP kernels against the reference's
+ * (double)n/(double)d > t  (resp. < t), in both forms the device has:
+ *   compare form (dswx_device.h quot_gt / quot_lt: the direct and generic kernels)
  *     gt:  (fma(-t, d, n) >  h_up * d) xor (d < 0),  h_up = (nextup(t) - t)/2
- *     lt:  (fma(-t, d, n) < -h_dn * d) xor (d < 0),  h_dn = (t - nextdown(t))/2
- *     (2^-100 replaces the half gap at t == 0, where it is not representable)
- * differs from the reference's  (double)n/(double)d > t  (resp. < t).
- * Returns the mismatch count (expected 0); first mismatch in bad_n/bad_d.
+ *     lt:  (fma(-t, d, n) <  h_dn * d) xor (d < 0),  h_dn = -(t - nextdown(t))/2
+ *   sign-bit form (dswx_tables.h lut_group: the table-driven kernel), a second fused
+ *   rounding instead of a multiply and a compare
+ *     gt:  signbit(fma( h_up, d, -r)) xor (d < 0),   r = fma(-t, d, n)
+ *     lt:  signbit(fma(-h_dn, d,  r)) xor (d < 0)
+ *   (2^-100 replaces the half gap at t == 0, where it is not representable)
+ * This file is built without contraction, and fma() is the IEEE operation v_fma_f64 is.
+ * The h constants are this file's own statement of those dswx_make_dev_params derives.
+ * `forms`: bit 0 = check the compare form, bit 1 = the sign-bit form.
  */
-int64_t oracle_check_quotient_predicate(double t, int less_than, int n_lo, int n_hi, int* bad_n,
-                                        int* bad_d) {
-    /* same constants as make_dev_params() in proteus_amd/csrc/dswx_hip.hip */
-    const double h_up = t == 0.0 ? ldexp(1.0, -100) : (nextafter(t, INFINITY) - t) * 0.5;
-    const double h_dn = t == 0.0 ? -ldexp(1.0, -100) : -((t - nextafter(t, -INFINITY)) * 0.5);
+typedef struct { double t, h_up, h_dn; int less_than; } quot_check_t;
+
+static quot_check_t quot_check_of(double t, int less_than) {
+    quot_check_t c;
+    c.t = t;
+    c.h_up = t == 0.0 ? ldexp(1.0, -100) : (nextafter(t, INFINITY) - t) * 0.5;
+    c.h_dn = t == 0.0 ? -ldexp(1.0, -100) : -((t - nextafter(t, -INFINITY)) * 0.5);
+    c.less_than = less_than;
+    return c;
+}
+
+/* 1 when a checked form differs from the reference at (n, d) */
+static inline __attribute__((always_inline)) int quot_mismatch(const quot_check_t* c, int forms, int n, int d) {
+    const double dn = (double)n, dd = (double)d;
+    volatile double q = dn / dd; /* numpy: inf / nan for d == 0 */
+    const double r = fma(-c->t, dd, dn);
+    int ref, cmp, sgn;
+    if (c->less_than) {
+        ref = q < c->t;
+        cmp = (r < c->h_dn * dd) != (d < 0);
+        sgn = (signbit(fma(-c->h_dn, dd, r)) != 0) != (d < 0);
+    } else {
+        ref = q > c->t;
+        cmp = (r > c->h_up * dd) != (d < 0);
+        sgn = (signbit(fma(c->h_up, dd, -r)) != 0) != (d < 0);
+    }
+    return ((forms & 1) && cmp != ref) || ((forms & 2) && sgn != ref);
+}
+
+/*
+ * Every (n, d) in int16 x int16 with n in [n_lo, n_hi).  Returns the mismatch
+ * count (expected 0); first mismatch in bad_n/bad_d.
+ */
+static inline __attribute__((always_inline)) int64_t quot_enumerate(const quot_check_t* c, int forms, int n_lo, int n_hi,
+                                                                    int* bad_n, int* bad_d) {
     int64_t bad = 0;
     for (int n = n_lo; n < n_hi; ++n) {
-        const double dn = (double)n;
         for (int d = -32768; d <= 32767; ++d) {
-            const double dd = (double)d;
-            volatile double q = dn / dd; /* numpy: inf / nan for d == 0 */
-            const double r = fma(-t, dd, dn);
-            int ref, got;
-            if (less_than) {
-                ref = q < t;
-                got = (r < h_dn * dd) != (d < 0);
-            } else {
-                ref = q > t;
-                got = (r > h_up * dd) != (d < 0);
-            }
-            if (ref != got) {
+            if (quot_mismatch(c, forms, n, d)) {
                 if (bad == 0) { if (bad_n) *bad_n = n; if (bad_d) *bad_d = d; }
                 ++bad;
             }
+        }
+    }
+    return bad;
+}
+
+int64_t oracle_check_quotient_predicate(double t, int less_than, int forms, int n_lo, int n_hi, int* bad_n,
+                                        int* bad_d) {
+    const quot_check_t c = quot_check_of(t, less_than);
+    switch (forms & 3) { /* a loop per selection, so that the form not asked for costs nothing */
+        case 1: return quot_enumerate(&c, 1, n_lo, n_hi, bad_n, bad_d);
+        case 2: return quot_enumerate(&c, 2, n_lo, n_hi, bad_n, bad_d);
+        case 3: return quot_enumerate(&c, 3, n_lo, n_hi, bad_n, bad_d);
+        default: return 0;
+    }
+}
+
+/* The same on a list of `count` pairs. */
+int64_t oracle_check_quotient_pairs(double t, int less_than, int forms, int64_t count, const int16_t* n,
+                                    const int16_t* d, int* bad_n, int* bad_d) {
+    const quot_check_t c = quot_check_of(t, less_than);
+    int64_t bad = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        if (quot_mismatch(&c, forms, n[i], d[i])) {
+            if (bad == 0) { if (bad_n) *bad_n = n[i]; if (bad_d) *bad_d = d[i]; }
+            ++bad;
         }
     }
     return bad;

@@ -102,19 +102,23 @@ def test_diag_vectors_wide_c(tag):
 
 
 def _predicate_job(args):
-    t, lt, lo, hi = args
-    return c_oracle.check_quotient_predicate(t, lt, lo, hi)
+    t, lt, lo, hi, forms = args
+    return c_oracle.check_quotient_predicate(t, lt, lo, hi, forms=forms)
 
 
 def test_quotient_predicate_exhaustive():
-    """All 2^32 (n, d) int16 pairs, every default threshold and awkward ones."""
+    """All 2^32 (n, d) int16 pairs, every default threshold and awkward ones: the compare form of the device predicate
+    (quot_gt / quot_lt) for all 19, and in the same pass its sign-bit form (lut_group) for the four defaults and 0.0 -- a
+    mismatch of either counts.  (Both forms for all 19 pass as well, at 1.8 times the wall time of the compare form alone;
+    tests/test_quotient_domain.py has both forms on the deciding pairs of every threshold of the domain.)"""
     c_oracle.build()
     cases = [(0.124, 0), (-0.44, 0), (-0.5, 0), (0.7, 1),         # defaults
              (0.0, 0), (0.0, 1), (1.0 / 3.0, 0), (2.0 / 3.0, 1), (-1.0, 0), (1.0, 1),
              (0.1, 0), (-0.3, 0), (0.55, 1), (0.25, 0), (0.25, 1), (1e-280, 0), (-1e-280, 1),
              (3.0, 0), (-7.5, 1)]
     chunks = [(-32768 + k * 4096, -32768 + (k + 1) * 4096) for k in range(16)]
-    jobs = [(t, lt, lo, hi) for (t, lt) in cases for (lo, hi) in chunks]
+    both = cases[:6]                                  # the defaults and 0.0, either direction
+    jobs = [(t, lt, lo, hi, c_oracle.BOTH_FORMS if (t, lt) in both else 1) for (t, lt) in cases for (lo, hi) in chunks]
     with cf.ProcessPoolExecutor(max_workers=8) as ex:
         results = list(ex.map(_predicate_job, jobs, chunksize=4))
     bad = [(j, r) for j, r in zip(jobs, results) if r[0] != 0]
