@@ -489,7 +489,7 @@ def landcover_mask_from_warped(worldcover_up3, copernicus, forest_classes, mask_
     thr = LANDCOVER_THRESHOLDS[mask_type.lower()] if thresholds is None else [int(t) for t in thresholds]
     off = year - 2000
     # the two developed classes are stored through the uint8 array: under the reference's pinned numpy 1.23.5 a class
-    # outside 0..255 wraps modulo 256 (numpy 2 raises OverflowError instead); the kernel's land_args does the same wrap
+    # outside 0..255 wraps modulo 256 (numpy 2 raises OverflowError instead); the library's land_check does the same wrap
     land[tree >= thr[0]] = LAND_EVERGREEN
     land[urban >= thr[1]] = (LAND_LOW_DEV0 + off) & 0xff
     land[urban >= thr[2]] = (LAND_HIGH_DEV0 + off) & 0xff

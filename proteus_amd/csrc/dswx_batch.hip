@@ -326,20 +326,15 @@ int dswx_batch_checksum(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int
     if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const size_t bytes = (size_t)n_planes * (size_t)n_tiles * sizeof(uint64_t);
+    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
     uint64_t* dev = nullptr;
-    HIP_TRY(dswx_locked_malloc(&dev, bytes));
-    int rc = dswx_checksum_launch(ctx, planes, n_planes, n_tiles, dev, s);
-    if (rc == DSWX_OK) {
-        hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = dswx_fail(DSWX_ERR_HIP, "dswx_batch_checksum: reading the checksums failed: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(s);         // whatever was queued must not outlive the allocation
-    }
-    (void)hipFree(dev);
-    return rc;
+    HIP_TRY(scratch.take(&dev, bytes));
+    if (int rc = dswx_checksum_launch(ctx, planes, n_planes, n_tiles, dev, scratch.s)) return rc;
+    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
+    if (e == hipSuccess) e = scratch.sync();
+    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_checksum: reading the checksums failed: %s", hipGetErrorString(e));
+    return DSWX_OK;
 }
 
 // The selected planes of two resident batches compared pair by pair (dswx_compare.hip), one launch; like the checksums the
@@ -377,20 +372,15 @@ int dswx_batch_compare(dswx_batch_t* a, dswx_batch_t* b, uint32_t plane_mask, in
     if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
     dswx_ctx* ctx = a->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
     const size_t bytes = (size_t)n_pairs * (size_t)n_tiles * sizeof(dswx_compare_t);
+    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
     dswx_compare_t* dev = nullptr;
-    HIP_TRY(dswx_locked_malloc(&dev, bytes));
-    int rc = dswx_compare_launch(ctx, pairs, n_pairs, n_tiles, atol, rtol, equal_nan, dev, s);
-    if (rc == DSWX_OK) {
-        hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = dswx_fail(DSWX_ERR_HIP, "dswx_batch_compare: reading the records failed: %s", hipGetErrorString(e));
-    } else {
-        (void)hipStreamSynchronize(s);         // whatever was queued must not outlive the allocation
-    }
-    (void)hipFree(dev);
-    return rc;
+    HIP_TRY(scratch.take(&dev, bytes));
+    if (int rc = dswx_compare_launch(ctx, pairs, n_pairs, n_tiles, atol, rtol, equal_nan, dev, scratch.s)) return rc;
+    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
+    if (e == hipSuccess) e = scratch.sync();
+    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_compare: reading the records failed: %s", hipGetErrorString(e));
+    return DSWX_OK;
 }
 
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch

@@ -199,7 +199,7 @@ int dswx_checksum_device(dswx_ctx_t* ctx, const void* plane, int32_t elem_bytes,
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     const dswx_checksum_plane pl = {plane, (uint64_t)n_elems * (uint64_t)elem_bytes, (uint64_t)tile_stride_elems * (uint64_t)elem_bytes};
-    return dswx_checksum_launch(ctx, &pl, 1, n_tiles, out, stream ? (hipStream_t)stream : ctx->stream);
+    return dswx_checksum_launch(ctx, &pl, 1, n_tiles, out, dswx_stream_of(ctx, stream));
 }
 
 }  // extern "C"

@@ -350,7 +350,7 @@ int dswx_compare_device(dswx_ctx_t* ctx, const void* a, const void* b, int32_t k
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     const dswx_compare_pair pr = {a, b, kind, (uint64_t)n_elems, (uint64_t)a_stride_elems, (uint64_t)b_stride_elems};
-    return dswx_compare_launch(ctx, &pr, 1, n_tiles, atol, rtol, equal_nan, out, stream ? (hipStream_t)stream : ctx->stream);
+    return dswx_compare_launch(ctx, &pr, 1, n_tiles, atol, rtol, equal_nan, out, dswx_stream_of(ctx, stream));
 }
 
 }  // extern "C"

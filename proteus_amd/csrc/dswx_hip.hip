@@ -721,7 +721,7 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     ClassifyPlan pl = {};
-    hipStream_t s = pl.s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = pl.s = dswx_stream_of(ctx, stream);
     if (n_tiles == 0 || n_pixels == 0) {
         if (counters && n_tiles > 0) HIP_TRY(hipMemsetAsync(counters, 0, (size_t)n_tiles * 3 * sizeof(int64_t), s));
         ctx->last_kernel = "none (empty input)";
@@ -868,7 +868,7 @@ int dswx_memset_d(dswx_ctx_t* ctx, void* dst, int value, size_t bytes) {
 int dswx_stream_synchronize(dswx_ctx_t* ctx, void* stream) {
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream));
+    HIP_TRY(hipStreamSynchronize(dswx_stream_of(ctx, stream)));
     return DSWX_OK;
 }
 
@@ -890,7 +890,7 @@ int dswx_event_destroy(dswx_ctx_t* ctx, void* event) {
 int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream) {
     if (!ctx || !event) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord((hipEvent_t)event, stream ? (hipStream_t)stream : ctx->stream));
+    HIP_TRY(hipEventRecord((hipEvent_t)event, dswx_stream_of(ctx, stream)));
     return DSWX_OK;
 }
 

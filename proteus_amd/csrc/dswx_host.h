@@ -108,6 +108,37 @@ static inline hipError_t dswx_locked_malloc(T** p, size_t n) {
     return hipMalloc(reinterpret_cast<void**>(p), n);
 }
 
+// The stream of an entry that takes one: the caller's, or the context's own for NULL.
+static inline hipStream_t dswx_stream_of(const dswx_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// Device memory that one call owns: up to four allocations, used on ONE stream and freed when the call returns, however
+// it returns.  What is queued must not outlive the allocation: unless the call's last act on the stream was a successful
+// sync(), the destructor waits for the stream (result ignored: nothing is left to do about it) before it frees.
+struct dswx_call_scratch {
+    hipStream_t s;
+    void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    int n = 0;
+    bool queued = false;      // work may have been queued on `s` since the last successful sync()
+    explicit dswx_call_scratch(hipStream_t stream) : s(stream) {}
+    dswx_call_scratch(const dswx_call_scratch&) = delete;      // one owner: the call
+    template <typename T>
+    hipError_t take(T** out, size_t bytes) {
+        if (n == 4) return hipErrorOutOfMemory;
+        const hipError_t e = dswx_locked_malloc(out, bytes);
+        if (e == hipSuccess) { p[n++] = *out; queued = true; }
+        return e;
+    }
+    hipError_t sync() {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e == hipSuccess) queued = false;
+        return e;
+    }
+    ~dswx_call_scratch() {
+        if (queued) (void)hipStreamSynchronize(s);
+        for (int i = 0; i < n; ++i) (void)hipFree(p[i]);
+    }
+};
+
 static inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Grows workspace `w` of a context to at least `need` bytes (dswx_hip.hip): the one place a workspace is freed and

@@ -460,28 +460,26 @@ __global__ __launch_bounds__(256) void dswx_synth_v1(dswx_planes_in_t in, unsign
 // ==============================================================================
 extern "C" {
 
+// DSWX_ERR_HIP under the name of the host entry that failed; the call-owned scratch cleans up behind the return
+#define ENTRY_TRY(entry, expr)                                                                                      \
+    do {                                                                                                            \
+        if (hipError_t e__ = (expr)) return dswx_fail(DSWX_ERR_HIP, entry ": %s", hipGetErrorString(e__));          \
+    } while (0)
+
 int dswx_interpret_layer_host(dswx_ctx_t* ctx, const int64_t* diag_decimal, int64_t n, uint8_t* out) {
     if (!ctx || (n > 0 && (!diag_decimal || !out))) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (n < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
     if (n == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    HIP_TRY(dswx_locked_malloc(&d_in, (size_t)n * 8));
-    hipError_t e = dswx_locked_malloc(&d_out, (size_t)n);
-    if (e != hipSuccess) { (void)hipFree(d_in); return dswx_fail(DSWX_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
-    hipStream_t s = ctx->stream;
-    e = hipMemcpyAsync(d_in, diag_decimal, (size_t)n * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(dswx_interpret_v1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                           static_cast<const long long*>(d_in), static_cast<uint8_t*>(d_out), (long long)n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_interpret_layer_host: %s", hipGetErrorString(e));
+    dswx_call_scratch scratch(ctx->stream);
+    long long* d_in = nullptr; uint8_t* d_out = nullptr;
+    ENTRY_TRY("dswx_interpret_layer_host", scratch.take(&d_in, (size_t)n * 8));
+    ENTRY_TRY("dswx_interpret_layer_host", scratch.take(&d_out, (size_t)n));
+    ENTRY_TRY("dswx_interpret_layer_host", hipMemcpyAsync(d_in, diag_decimal, (size_t)n * 8, hipMemcpyHostToDevice, scratch.s));
+    hipLaunchKernelGGL(dswx_interpret_v1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, scratch.s, d_in, d_out, (long long)n);
+    ENTRY_TRY("dswx_interpret_layer_host", hipGetLastError());
+    ENTRY_TRY("dswx_interpret_layer_host", hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, scratch.s));
+    ENTRY_TRY("dswx_interpret_layer_host", scratch.sync());
     return DSWX_OK;
 }
 
@@ -533,9 +531,14 @@ int dswx_shadow_thresholds(double min_slope_angle, double max_sun_local_inc_angl
     return DSWX_OK;
 }
 
-static int shadow_args(ShadowArgs* a, int64_t height, int64_t width, int64_t margin, const double sun_vector[3],
-                       double sin_azimuth, double cos_azimuth, double slope_arg_max, double inc_q_min,
-                       double pixel_spacing_x, double pixel_spacing_y) {
+// The one validated request of a shadow call: every refusal of the seven entries, then `a` complete for shadow_launch
+// (a host entry passes its host rasters, one tile and no stride, and swaps the device copies in afterwards).
+static int shadow_check(ShadowArgs* a, dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
+                        int64_t margin, const double sun_vector[3], double sin_azimuth, double cos_azimuth,
+                        double slope_arg_max, double inc_q_min, double pixel_spacing_x, double pixel_spacing_y,
+                        uint8_t* shadow, int64_t shadow_tile_stride) {
+    if (!ctx || !dem || !shadow) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
+    if (n_tiles < 0 || n_tiles > 65535) return dswx_fail(DSWX_ERR_ARG, "n_tiles out of range");
     if (!sun_vector) return dswx_fail(DSWX_ERR_ARG, "sun_vector is NULL");
     if (height < 2 || width < 2)
         return dswx_fail(DSWX_ERR_ARG, "Shape of array too small to calculate a numerical gradient, "
@@ -543,9 +546,16 @@ static int shadow_args(ShadowArgs* a, int64_t height, int64_t width, int64_t mar
     if (margin < 0 || 2 * margin >= height || 2 * margin >= width) return dswx_fail(DSWX_ERR_ARG, "bad margin");
     if (height > 2147483647LL / width) return dswx_fail(DSWX_ERR_ARG, "DEM larger than 2^31 pixels");
     if (std::isnan(slope_arg_max) || std::isnan(inc_q_min)) return dswx_fail(DSWX_ERR_ARG, "shadow threshold is NaN");
+    const long long ow = width - 2 * margin, oh = height - 2 * margin;
+    if (n_tiles != 0) {          // a call without tiles is no work, whatever its stride
+        if (shadow_tile_stride != 0 && shadow_tile_stride < oh * ow)
+            return dswx_fail(DSWX_ERR_ARG, "shadow_tile_stride smaller than the shadow raster");
+        if ((oh + 3) / 4 > 65535) return dswx_fail(DSWX_ERR_ARG, "raster too tall for one launch");
+    }
+    a->dem = dem; a->shadow = shadow;
     a->height = height; a->width = width; a->margin = margin;
-    a->spacing_x = (float)pixel_spacing_x;
-    a->neg_abs_spacing_y = (float)(-std::fabs(pixel_spacing_y));
+    a->out_stride = shadow_tile_stride ? shadow_tile_stride : oh * ow;
+    a->spacing_x = (float)pixel_spacing_x; a->neg_abs_spacing_y = (float)(-std::fabs(pixel_spacing_y));
     for (int i = 0; i < 3; ++i) a->sun[i] = sun_vector[i];
     a->sin_az = sin_azimuth; a->cos_az = cos_azimuth;
     a->slope_arg_max = slope_arg_max; a->inc_q_min = inc_q_min;
@@ -600,29 +610,15 @@ static void shadow_filter(const ShadowArgs& a, bool f32, ShadowFilter* f) {
     }
 }
 
-static int shadow_device_impl(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
-                              int64_t margin, const double sun_vector[3], double sin_azimuth,
-                              double cos_azimuth, double slope_arg_max, double inc_q_min,
-                              double pixel_spacing_x, double pixel_spacing_y, uint8_t* shadow, void* stream,
-                              bool f32, int64_t shadow_tile_stride = 0) {
-    if (!ctx || !dem || !shadow) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
-    if (n_tiles < 0 || n_tiles > 65535) return dswx_fail(DSWX_ERR_ARG, "n_tiles out of range");
-    ShadowArgs a;
-    int rc = shadow_args(&a, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max, inc_q_min,
-                         pixel_spacing_x, pixel_spacing_y);
-    if (rc) return rc;
+// The dispatch of a checked request on stream `s`; asynchronous.
+static int shadow_launch(dswx_ctx_t* ctx, const ShadowArgs& req, int64_t n_tiles, bool f32, hipStream_t s) {
     if (n_tiles == 0) return DSWX_OK;
-    a.dem = dem; a.shadow = shadow;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    const long long ow = width - 2 * margin, oh = height - 2 * margin;
-    if (shadow_tile_stride != 0 && shadow_tile_stride < oh * ow)
-        return dswx_fail(DSWX_ERR_ARG, "shadow_tile_stride smaller than the shadow raster");
-    a.out_stride = shadow_tile_stride ? shadow_tile_stride : oh * ow;
-    if ((oh + 3) / 4 > 65535) return dswx_fail(DSWX_ERR_ARG, "raster too tall for one launch");
+    ShadowArgs a = req;          // by_first / by_step change per pass
+    const long long margin = a.margin, ow = a.width - 2 * margin, oh = a.height - 2 * margin;
     // four pixels per thread behind the filter wherever a quad and the columns beside it are interior pixels (unaligned
     // 8-byte loads / dword stores: any margin >= 2, any width, any buffer alignment -- see dswx_shadow_v3)
-    const bool quads = margin >= 2 && ow >= 4 && aligned_to(dem, 4) && ctx->shadow_kernel != 2;
+    const bool quads = margin >= 2 && ow >= 4 && aligned_to(a.dem, 4) && ctx->shadow_kernel != 2;
     if (quads) {
         ShadowFilter f;
         shadow_filter(a, f32, &f);
@@ -656,21 +652,42 @@ static int shadow_device_impl(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles
     return DSWX_OK;
 }
 
+// A checked request whose rasters are host memory: one tile staged through device memory of this call's own, synchronous.
+static int shadow_host_run(dswx_ctx_t* ctx, ShadowArgs a, bool f32) {
+    const float* dem = a.dem; uint8_t* shadow = a.shadow;          // the caller's rasters
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t in_bytes = (size_t)a.height * (size_t)a.width * 4;
+    const size_t out_px = (size_t)(a.height - 2 * a.margin) * (size_t)(a.width - 2 * a.margin);
+    dswx_call_scratch scratch(ctx->stream);
+    float* d_dem = nullptr; uint8_t* d_out = nullptr;
+    ENTRY_TRY("dswx_shadow_layer_host", scratch.take(&d_dem, in_bytes));
+    ENTRY_TRY("dswx_shadow_layer_host", scratch.take(&d_out, out_px));
+    ENTRY_TRY("dswx_shadow_layer_host", hipMemcpyAsync(d_dem, dem, in_bytes, hipMemcpyHostToDevice, scratch.s));
+    a.dem = d_dem; a.shadow = d_out;
+    if (int rc = shadow_launch(ctx, a, 1, f32, scratch.s)) return rc;
+    ENTRY_TRY("dswx_shadow_layer_host", hipMemcpyAsync(shadow, d_out, out_px, hipMemcpyDeviceToHost, scratch.s));
+    ENTRY_TRY("dswx_shadow_layer_host", scratch.sync());
+    return DSWX_OK;
+}
+
 int dswx_shadow_layer_device_q(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
                                int64_t margin, const double sun_vector[3], double sin_azimuth,
                                double cos_azimuth, double slope_arg_max, double inc_q_min,
                                double pixel_spacing_x, double pixel_spacing_y, uint8_t* shadow, void* stream) {
-    return shadow_device_impl(ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
-                              slope_arg_max, inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, stream, false);
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
+                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_launch(ctx, a, n_tiles, false, dswx_stream_of(ctx, stream));
 }
 
 int dswx_shadow_layer_device_q32(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
                                  int64_t margin, const double sun_vector[3], double sin_azimuth,
                                  double cos_azimuth, float slope_arg_max, float inc_q_min,
                                  double pixel_spacing_x, double pixel_spacing_y, uint8_t* shadow, void* stream) {
-    return shadow_device_impl(ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
-                              (double)slope_arg_max, (double)inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow,
-                              stream, true);
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
+                              (double)slope_arg_max, (double)inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_launch(ctx, a, n_tiles, true, dswx_stream_of(ctx, stream));
 }
 
 int dswx_shadow_layer_device(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
@@ -678,58 +695,41 @@ int dswx_shadow_layer_device(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles,
                              double cos_azimuth, double min_slope_angle, double max_sun_local_inc_angle,
                              double pixel_spacing_x, double pixel_spacing_y, uint8_t* shadow, void* stream) {
     double slope_arg_max, inc_q_min;
-    int rc = dswx_shadow_thresholds(min_slope_angle, max_sun_local_inc_angle, &slope_arg_max, &inc_q_min);
-    if (rc) return rc;
-    return dswx_shadow_layer_device_q(ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
-                                      slope_arg_max, inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, stream);
+    if (int rc = dswx_shadow_thresholds(min_slope_angle, max_sun_local_inc_angle, &slope_arg_max, &inc_q_min)) return rc;
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
+                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_launch(ctx, a, n_tiles, false, dswx_stream_of(ctx, stream));
 }
 
-static int shadow_host_impl(dswx_ctx_t* ctx, const float* dem, int64_t height, int64_t width, int64_t margin,
-                            const double sun_vector[3], double sin_azimuth, double cos_azimuth,
-                            double slope_arg_max, double inc_q_min, double pixel_spacing_x,
-                            double pixel_spacing_y, uint8_t* shadow, bool f32) {
-    if (!ctx || !dem || !shadow) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
-    ShadowArgs chk;
-    int rc = shadow_args(&chk, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max, inc_q_min,
-                         pixel_spacing_x, pixel_spacing_y);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t in_bytes = (size_t)height * (size_t)width * 4;
-    const size_t out_px = (size_t)(height - 2 * margin) * (size_t)(width - 2 * margin);
-    void* d_dem = nullptr;
-    void* d_out = nullptr;
-    HIP_TRY(dswx_locked_malloc(&d_dem, in_bytes));
-    hipError_t e = dswx_locked_malloc(&d_out, out_px);
-    hipStream_t s = ctx->stream;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_dem, dem, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        rc = shadow_device_impl(ctx, static_cast<const float*>(d_dem), 1, height, width, margin, sun_vector,
-                                sin_azimuth, cos_azimuth, slope_arg_max, inc_q_min, pixel_spacing_x,
-                                pixel_spacing_y, static_cast<uint8_t*>(d_out), s, f32);
-        if (rc == DSWX_OK) e = hipMemcpyAsync(shadow, d_out, out_px, hipMemcpyDeviceToHost, s);
-        if (rc == DSWX_OK && e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    (void)hipFree(d_dem);
-    if (d_out) (void)hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_shadow_layer_host: %s", hipGetErrorString(e));
-    return DSWX_OK;
+int dswx_shadow_layer_batch(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
+                            int64_t margin, const double sun_vector[3], double sin_azimuth, double cos_azimuth,
+                            double slope_arg_max, double inc_q_min, int32_t float32_arithmetic, double pixel_spacing_x,
+                            double pixel_spacing_y, uint8_t* shadow, int64_t shadow_tile_stride, void* stream) {
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
+                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, shadow_tile_stride)) return rc;
+    return shadow_launch(ctx, a, n_tiles, float32_arithmetic != 0, dswx_stream_of(ctx, stream));
 }
 
 int dswx_shadow_layer_host_q(dswx_ctx_t* ctx, const float* dem, int64_t height, int64_t width, int64_t margin,
                              const double sun_vector[3], double sin_azimuth, double cos_azimuth,
                              double slope_arg_max, double inc_q_min, double pixel_spacing_x,
                              double pixel_spacing_y, uint8_t* shadow) {
-    return shadow_host_impl(ctx, dem, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
-                            inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, false);
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, 1, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
+                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_host_run(ctx, a, false);
 }
 
 int dswx_shadow_layer_host_q32(dswx_ctx_t* ctx, const float* dem, int64_t height, int64_t width, int64_t margin,
                                const double sun_vector[3], double sin_azimuth, double cos_azimuth,
                                float slope_arg_max, float inc_q_min, double pixel_spacing_x,
                                double pixel_spacing_y, uint8_t* shadow) {
-    return shadow_host_impl(ctx, dem, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
-                            (double)slope_arg_max, (double)inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, true);
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, 1, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
+                              (double)slope_arg_max, (double)inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_host_run(ctx, a, true);
 }
 
 int dswx_shadow_layer_host(dswx_ctx_t* ctx, const float* dem, int64_t height, int64_t width, int64_t margin,
@@ -737,14 +737,21 @@ int dswx_shadow_layer_host(dswx_ctx_t* ctx, const float* dem, int64_t height, in
                            double min_slope_angle, double max_sun_local_inc_angle, double pixel_spacing_x,
                            double pixel_spacing_y, uint8_t* shadow) {
     double slope_arg_max, inc_q_min;
-    int rc = dswx_shadow_thresholds(min_slope_angle, max_sun_local_inc_angle, &slope_arg_max, &inc_q_min);
-    if (rc) return rc;
-    return dswx_shadow_layer_host_q(ctx, dem, height, width, margin, sun_vector, sin_azimuth, cos_azimuth,
-                                    slope_arg_max, inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow);
+    if (int rc = dswx_shadow_thresholds(min_slope_angle, max_sun_local_inc_angle, &slope_arg_max, &inc_q_min)) return rc;
+    ShadowArgs a;
+    if (int rc = shadow_check(&a, ctx, dem, 1, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
+                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, 0)) return rc;
+    return shadow_host_run(ctx, a, false);
 }
 
-static int land_args(LandArgs* a, int64_t height, int64_t width, const int32_t* forest_classes,
-                     int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset) {
+// ---- landcover mask: the one validated request of a call (as shadow_check), then its dispatch ------------------------------
+static int land_check(LandArgs* a, dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus, int64_t n_tiles,
+                      int64_t height, int64_t width, const int32_t* forest_classes, int32_t n_forest_classes,
+                      const int32_t thresholds[4], int32_t year_offset, uint8_t* land, int64_t land_tile_stride) {
+    if (!ctx || !worldcover_up3 || !copernicus || !land) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
+    if (land_tile_stride != 0 && land_tile_stride < height * width)
+        return dswx_fail(DSWX_ERR_ARG, "land_tile_stride smaller than the raster");
+    if (n_tiles < 0 || n_tiles > 65535) return dswx_fail(DSWX_ERR_ARG, "n_tiles out of range");
     if (!thresholds) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     if (height < 0 || width < 0 || n_forest_classes < 0 || (n_forest_classes > 0 && !forest_classes))
         return dswx_fail(DSWX_ERR_ARG, "bad size");
@@ -759,57 +766,17 @@ static int land_args(LandArgs* a, int64_t height, int64_t width, const int32_t* 
     a->low_class = (int)(uint8_t)(0u + (uint32_t)year_offset);
     a->high_class = (int)(uint8_t)(100u + (uint32_t)year_offset);
     a->height = height; a->width = width;
+    a->wc3 = worldcover_up3; a->cgls = copernicus; a->land = land;
+    a->out_stride = land_tile_stride ? land_tile_stride : height * width;
     return DSWX_OK;
 }
 
-static int landcover_device_impl(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
-                                 int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
-                                 int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
-                                 uint8_t* land, int64_t land_tile_stride, void* stream);
-
-int dswx_landcover_mask_device(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
-                               int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
-                               int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
-                               uint8_t* land, void* stream) {
-    return landcover_device_impl(ctx, worldcover_up3, copernicus, n_tiles, height, width, forest_classes, n_forest_classes,
-                                 thresholds, year_offset, land, 0, stream);
-}
-
-int dswx_landcover_mask_batch(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
-                              int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
-                              int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
-                              uint8_t* land, int64_t land_tile_stride, void* stream) {
-    return landcover_device_impl(ctx, worldcover_up3, copernicus, n_tiles, height, width, forest_classes, n_forest_classes,
-                                 thresholds, year_offset, land, land_tile_stride, stream);
-}
-
-int dswx_shadow_layer_batch(dswx_ctx_t* ctx, const float* dem, int64_t n_tiles, int64_t height, int64_t width,
-                            int64_t margin, const double sun_vector[3], double sin_azimuth, double cos_azimuth,
-                            double slope_arg_max, double inc_q_min, int32_t float32_arithmetic, double pixel_spacing_x,
-                            double pixel_spacing_y, uint8_t* shadow, int64_t shadow_tile_stride, void* stream) {
-    return shadow_device_impl(ctx, dem, n_tiles, height, width, margin, sun_vector, sin_azimuth, cos_azimuth, slope_arg_max,
-                              inc_q_min, pixel_spacing_x, pixel_spacing_y, shadow, stream, float32_arithmetic != 0,
-                              shadow_tile_stride);
-}
-
-static int landcover_device_impl(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
-                                 int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
-                                 int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
-                                 uint8_t* land, int64_t land_tile_stride, void* stream) {
-    if (!ctx || !worldcover_up3 || !copernicus || !land) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
-    if (land_tile_stride != 0 && land_tile_stride < height * width)
-        return dswx_fail(DSWX_ERR_ARG, "land_tile_stride smaller than the raster");
-    if (n_tiles < 0 || n_tiles > 65535) return dswx_fail(DSWX_ERR_ARG, "n_tiles out of range");
-    LandArgs a;
-    int rc = land_args(&a, height, width, forest_classes, n_forest_classes, thresholds, year_offset);
-    if (rc) return rc;
+static int land_launch(dswx_ctx_t* ctx, const LandArgs& a, int64_t n_tiles, hipStream_t s) {
+    const long long height = a.height, width = a.width;
     if (n_tiles == 0 || height == 0 || width == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
-    a.wc3 = worldcover_up3; a.cgls = copernicus; a.land = land;
-    a.out_stride = land_tile_stride ? land_tile_stride : height * width;
     // four pixels per thread with dword loads when rows keep 4-byte alignment
-    const bool quad = width % 4 == 0 && aligned_to(worldcover_up3, 4) && aligned_to(copernicus, 4) && aligned_to(land, 4) &&
+    const bool quad = width % 4 == 0 && aligned_to(a.wc3, 4) && aligned_to(a.cgls, 4) && aligned_to(a.land, 4) &&
                       a.out_stride % 4 == 0;
     if (quad) {
         static_assert(LAND_ROWS == 1, "the flat quad numbering assumes one row per thread");
@@ -826,38 +793,47 @@ static int landcover_device_impl(dswx_ctx_t* ctx, const uint8_t* worldcover_up3,
     return DSWX_OK;
 }
 
+int dswx_landcover_mask_device(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
+                               int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
+                               int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
+                               uint8_t* land, void* stream) {
+    LandArgs a;
+    if (int rc = land_check(&a, ctx, worldcover_up3, copernicus, n_tiles, height, width, forest_classes, n_forest_classes,
+                            thresholds, year_offset, land, 0)) return rc;
+    return land_launch(ctx, a, n_tiles, dswx_stream_of(ctx, stream));
+}
+
+int dswx_landcover_mask_batch(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
+                              int64_t n_tiles, int64_t height, int64_t width, const int32_t* forest_classes,
+                              int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
+                              uint8_t* land, int64_t land_tile_stride, void* stream) {
+    LandArgs a;
+    if (int rc = land_check(&a, ctx, worldcover_up3, copernicus, n_tiles, height, width, forest_classes, n_forest_classes,
+                            thresholds, year_offset, land, land_tile_stride)) return rc;
+    return land_launch(ctx, a, n_tiles, dswx_stream_of(ctx, stream));
+}
+
 int dswx_landcover_mask_host(dswx_ctx_t* ctx, const uint8_t* worldcover_up3, const uint8_t* copernicus,
                              int64_t height, int64_t width, const int32_t* forest_classes,
                              int32_t n_forest_classes, const int32_t thresholds[4], int32_t year_offset,
                              uint8_t* land) {
-    if (!ctx || !worldcover_up3 || !copernicus || !thresholds || !land) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
-    {
-        LandArgs chk;
-        int rc = land_args(&chk, height, width, forest_classes, n_forest_classes, thresholds, year_offset);
-        if (rc) return rc;
-    }
+    LandArgs a;
+    if (int rc = land_check(&a, ctx, worldcover_up3, copernicus, 1, height, width, forest_classes, n_forest_classes,
+                            thresholds, year_offset, land, 0)) return rc;
     if (height == 0 || width == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n = (size_t)height * (size_t)width;
-    void* d_wc = nullptr; void* d_cg = nullptr; void* d_out = nullptr;
-    hipError_t e = dswx_locked_malloc(&d_wc, 9 * n);
-    if (e == hipSuccess) e = dswx_locked_malloc(&d_cg, n);
-    if (e == hipSuccess) e = dswx_locked_malloc(&d_out, n);
-    hipStream_t s = ctx->stream;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_wc, worldcover_up3, 9 * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cg, copernicus, n, hipMemcpyHostToDevice, s);
-    int rc = DSWX_OK;
-    if (e == hipSuccess)
-        rc = dswx_landcover_mask_device(ctx, static_cast<const uint8_t*>(d_wc), static_cast<const uint8_t*>(d_cg), 1,
-                                        height, width, forest_classes, n_forest_classes, thresholds, year_offset,
-                                        static_cast<uint8_t*>(d_out), s);
-    if (e == hipSuccess && rc == DSWX_OK) e = hipMemcpyAsync(land, d_out, n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (d_wc) (void)hipFree(d_wc);
-    if (d_cg) (void)hipFree(d_cg);
-    if (d_out) (void)hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_landcover_mask_host: %s", hipGetErrorString(e));
+    dswx_call_scratch scratch(ctx->stream);
+    uint8_t* d_wc = nullptr; uint8_t* d_cg = nullptr; uint8_t* d_out = nullptr;
+    ENTRY_TRY("dswx_landcover_mask_host", scratch.take(&d_wc, 9 * n));
+    ENTRY_TRY("dswx_landcover_mask_host", scratch.take(&d_cg, n));
+    ENTRY_TRY("dswx_landcover_mask_host", scratch.take(&d_out, n));
+    ENTRY_TRY("dswx_landcover_mask_host", hipMemcpyAsync(d_wc, worldcover_up3, 9 * n, hipMemcpyHostToDevice, scratch.s));
+    ENTRY_TRY("dswx_landcover_mask_host", hipMemcpyAsync(d_cg, copernicus, n, hipMemcpyHostToDevice, scratch.s));
+    a.wc3 = d_wc; a.cgls = d_cg; a.land = d_out;
+    if (int rc = land_launch(ctx, a, 1, scratch.s)) return rc;
+    ENTRY_TRY("dswx_landcover_mask_host", hipMemcpyAsync(land, d_out, n, hipMemcpyDeviceToHost, scratch.s));
+    ENTRY_TRY("dswx_landcover_mask_host", scratch.sync());
     return DSWX_OK;
 }
 
@@ -873,7 +849,7 @@ static int synth_impl(dswx_ctx_t* ctx, uint64_t seed, int64_t tile0, int64_t n_t
     if (tile_stride < P) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
     if (n_tiles == 0 || P == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     const int64_t max_y = 65535;
     for (int64_t t0 = 0; t0 < n_tiles; t0 += max_y) {
         const int64_t nt = (n_tiles - t0 < max_y) ? n_tiles - t0 : max_y;

@@ -342,7 +342,7 @@ int dswx_cog_blocks_device(dswx_ctx_t* ctx, const void* plane, int32_t elem_byte
     if (!aligned_to(blocks, 16) || !aligned_to(plane, (size_t)elem_bytes))
         return dswx_fail(DSWX_ERR_ALIGN, "blocks must be 16-byte aligned, the plane aligned to its samples");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     if (elem_bytes == 4) {
         if (predictor != 3) return dswx_fail(DSWX_ERR_UNSUPPORTED, "4-byte samples: Float32 with PREDICTOR=3 only");
         if (lay.n_levels != 1)
@@ -390,7 +390,7 @@ int dswx_untile_device(dswx_ctx_t* ctx, const void* blocks, int32_t elem_bytes, 
     if (!aligned_to(blocks, (size_t)elem_bytes) || !aligned_to(plane, (size_t)elem_bytes))
         return dswx_fail(DSWX_ERR_ALIGN, "buffers must be aligned to their samples");
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     UntileArgs a = {};
     a.blocks = blocks; a.dst = plane;
     a.height = (int)height; a.width = (int)width; a.bw = block_width; a.bh = block_height;
@@ -442,7 +442,7 @@ int dswx_copy_2d_device(dswx_ctx_t* ctx, void* dst, size_t dst_pitch_bytes, cons
     if (width_bytes == 0 || height == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemcpy2DAsync(dst, dst_pitch_bytes, src, src_pitch_bytes, width_bytes, height, hipMemcpyDeviceToDevice,
-                             stream ? (hipStream_t)stream : ctx->stream));
+                             dswx_stream_of(ctx, stream)));
     return DSWX_OK;
 }
 
@@ -455,7 +455,7 @@ int dswx_rgb_planes_device(dswx_ctx_t* ctx, const int16_t* red, const int16_t* g
         return dswx_fail(DSWX_ERR_ALIGN, "planes must be aligned to their samples");
     if (n_pixels == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     RgbArgs a = {};
     a.band[0] = red; a.band[1] = green; a.band[2] = blue;
     a.diag = diag; a.out = out; a.n = n_pixels; a.clip = clip_negative_reflectance != 0;
@@ -477,7 +477,7 @@ int dswx_gather_2d_device(dswx_ctx_t* ctx, const void* src, int32_t elem_bytes, 
         return dswx_fail(DSWX_ERR_ALIGN, "planes must be aligned to their samples, the index arrays to 4 bytes");
     if (n_rows == 0 || n_cols == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     const dim3 grid((unsigned)((n_cols + 255) / 256), (unsigned)n_rows), block(256);
     if (elem_bytes == 1)
         hipLaunchKernelGGL(dswx_gather_2d_v1<unsigned char>, grid, block, 0, s, static_cast<const unsigned char*>(src), (long long)src_width, rows, cols, n_cols, static_cast<unsigned char*>(dst));
@@ -495,7 +495,7 @@ int dswx_to_byte_device(dswx_ctx_t* ctx, const void* src, int32_t src_kind, int6
     if (!aligned_to(src, src_kind == 3 ? 4 : 2)) return dswx_fail(DSWX_ERR_ALIGN, "the plane must be aligned to its samples");
     if (n == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     const unsigned long long groups = ((unsigned long long)n + 255) / 256;
     if (groups > 0x7fffffffull) return dswx_fail(DSWX_ERR_ARG, "raster too large for one launch");
     const dim3 grid((unsigned)groups), block(256);
@@ -516,7 +516,7 @@ int dswx_convolve_axis_device(dswx_ctx_t* ctx, const void* src, int32_t src_is_f
         return dswx_fail(DSWX_ERR_ALIGN, "src / dst must be aligned to their samples, first to 4 bytes, weights to 8");
     if (n_lines == 0 || n_out == 0) return DSWX_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     ConvArgs a = {};
     a.src = src; a.dst = dst; a.first = first; a.w = weights;
     a.n_lines = n_lines; a.n_in = n_in; a.n_out = n_out; a.taps = taps;
@@ -538,14 +538,14 @@ int dswx_convolve_axis_device(dswx_ctx_t* ctx, const void* src, int32_t src_is_f
 int dswx_memcpy_h2d_async(dswx_ctx_t* ctx, void* dst, const void* src, size_t bytes, void* stream) {
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream ? (hipStream_t)stream : ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, dswx_stream_of(ctx, stream)));
     return DSWX_OK;
 }
 
 int dswx_memcpy_d2h_async(dswx_ctx_t* ctx, void* dst, const void* src, size_t bytes, void* stream) {
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream ? (hipStream_t)stream : ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, dswx_stream_of(ctx, stream)));
     return DSWX_OK;
 }
 

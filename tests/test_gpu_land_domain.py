@@ -63,7 +63,7 @@ def rule_of(wc, cg, forest, thr):
 
 
 def dispatch(width, offsets, stride):
-    """The host's choice between the kernels (landcover_device_impl): 'v3' or 'v1'."""
+    """The host's choice between the kernels (land_launch): 'v3' or 'v1'."""
     return 'v3' if width % 4 == 0 and all(off % 4 == 0 for off in offsets) and stride % 4 == 0 else 'v1'
 
 

@@ -687,7 +687,7 @@ int dswx_stream_probe(dswx_ctx_t* ctx, int64_t n_tiles, int64_t n_pixels, int64_
     for (int k = 0; k < 6; ++k)
         if (!in->band[k] || !aligned_to(in->band[k], 16)) return dswx_fail(DSWX_ERR_ALIGN, "band[%d]", k);
     HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    hipStream_t s = dswx_stream_of(ctx, stream);
     KArgs a;
     std::memset(&a, 0, sizeof a);
     a.in = *in; a.out = *out; a.n_pixels = n_pixels;
