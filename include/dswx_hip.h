@@ -635,6 +635,50 @@ int dswx_batch_compare(dswx_batch_t* batch_a, dswx_batch_t* batch_b, uint32_t pl
 int dswx_compare_host(const void* a, const void* b, int32_t kind, int64_t n_elems, double atol, double rtol,
                       int32_t equal_nan, dswx_compare_t* out_record);
 
+/* ---- histogram: how much of each value a plane holds, 256 counts per tile (additive to ABI v7) ------------------------
+ * A checksum says that a resident tile is what it should be, a comparison where two differ; these entries say what is IN a
+ * tile -- how many pixels are open water, partial water, snow, cloud, ocean-masked or fill, how often each of the five
+ * diagnostic tests fired, how the reflectances of a band are distributed -- again without the plane crossing PCIe: 2 KiB per
+ * tile and plane come back.  A C caller tests for them with DSWX_HAS_HISTOGRAM.
+ * THE DEFINITION.  One record per tile and plane is uint64_t bins[DSWX_HIST_BINS].  Only the first n_elems elements of a tile
+ * are counted, the padding up to the tile stride is never read.  The bin of an element v follows the plane's `kind`:
+ *   DSWX_HIST_U8                    (uint8 planes)  bin = the byte;
+ *   DSWX_HIST_U16, DSWX_HIST_I16    (uint16 / int16 planes)  linear, with `lo` (int32) and `shift` (0 .. 8): d = (int32)v - lo
+ *                                   as an integer; if 0 <= d < (256 << shift) the element is counted in bin d >> shift,
+ *                                   otherwise it is NOT COUNTED -- the bins sum to the number of elements in range;
+ *   DSWX_HIST_DIAG                  (uint16 planes in the saved DIAG form: the decimal digits of v are the five test bits,
+ *                                   _get_binary_representation, dswx_hls.py:4286-4317)  if every decimal digit of v is 0 or 1
+ *                                   and v <= 11111: bin = d0 + 2 d1 + 4 d2 + 8 d3 + 16 d4 (0 .. 31, d0 the units digit);
+ *                                   v == 65535 (nodata): bin 32; any other value: bin 33.  Bins 34 .. 255 stay zero.
+ * `lo` and `shift` are ignored for DSWX_HIST_U8 and DSWX_HIST_DIAG (a shift outside 0 .. 8 is refused for every kind).
+ * The counts are integer sums: they do not depend on the order of the blocks or of their atomic adds, so the device entries
+ * are deterministic. */
+#define DSWX_HAS_HISTOGRAM 1
+#define DSWX_HIST_BINS 256
+enum { DSWX_HIST_U8 = 0, DSWX_HIST_U16 = 1, DSWX_HIST_I16 = 2, DSWX_HIST_DIAG = 3, DSWX_HIST_KINDS = 4 };
+/* One plane [n_tiles][tile_stride_elems] in DEVICE memory -> out[n_tiles][DSWX_HIST_BINS] (device uint64).  Asynchronous on
+ * `stream` (NULL = the context's stream), no synchronisation inside: out is zeroed on the stream, then one kernel adds into
+ * it.  tile_stride_elems 0 = n_elems.  `kind` not a DSWX_HIST_* value, `shift` outside 0 .. 8, a negative size, tile count or
+ * stride, a stride below n_elems, or a NULL pointer with n_tiles > 0: DSWX_ERR_ARG; a plane off its element alignment, or
+ * `out` off 8 bytes: DSWX_ERR_ALIGN.  (The arguments are checked before the context is; the limits on the size of a plane
+ * are those of dswx_compare_device.) */
+int dswx_histogram_device(dswx_ctx_t* ctx, const void* plane, int32_t kind, int32_t lo, int32_t shift, int64_t n_tiles,
+                          int64_t n_elems, int64_t tile_stride_elems, uint64_t* out_device_u64, void* stream);
+/* The planes of a resident batch selected by `plane_mask` (bit k = plane DSWX_PLANE_k: inputs, layers, extra layers), tiles
+ * tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last), the height x width pixels of every tile ->
+ * out[popcount(plane_mask)][n_tiles][DSWX_HIST_BINS] in HOST memory, planes in ascending index order, complete on return.
+ * ONE kernel launch for all selected planes, on `stream`; the addresses are those of dswx_batch_planes, so packed,
+ * separate-output and placed batches are alike.  The kinds come from the library's plane table: the six bands are
+ * DSWX_HIST_I16 with band_lo / band_shift (0 and 6: reflectances 0 .. 16383 in bins of 64), DIAG is DSWX_HIST_DIAG, every
+ * other plane DSWX_HIST_U8.  DSWX_PLANE_COUNTERS in the mask: DSWX_ERR_ARG.  A plane the batch does not have: DSWX_ERR_ARG,
+ * and dswx_last_error() names it.  (The device words live in an allocation made and freed by the call.) */
+int dswx_batch_histogram(dswx_batch_t* batch, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, int32_t band_lo,
+                         int32_t band_shift, uint64_t* out_host_u64, void* stream);
+/* The same definition on a HOST buffer (any address) in plain scalar C++: needs no device and no context.  The other half
+ * of a comparison -- the counts of a host array or a decoded file -- not a fallback of the two entries above.
+ * out_u64_256 = uint64_t [DSWX_HIST_BINS], 8-byte aligned. */
+int dswx_histogram_host(const void* data, int32_t kind, int32_t lo, int32_t shift, int64_t n_elems, uint64_t* out_u64_256);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -662,8 +706,9 @@ int dswx_event_destroy(dswx_ctx_t* ctx, void* event);
 int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
-/* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* call on this
- * context selected (for profiles / DESIGN.md): writes a NUL-terminated string. */
+/* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram*
+ * call on this context selected (for profiles / DESIGN.md; the histogram's also names its replica count): writes a
+ * NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 
 #ifdef __cplusplus

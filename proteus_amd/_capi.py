@@ -38,9 +38,13 @@ EXPORTED_SYMBOLS = (
     'dswx_to_byte_device', 'dswx_gather_2d_device',
     'dswx_memcpy_h2d_async', 'dswx_memcpy_d2h_async',
     'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host',
-    'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host')
+    'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host',
+    'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
+HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
+HIST_U8, HIST_U16, HIST_I16, HIST_DIAG = range(4)
+HIST_BINS = 256
 
 
 class DswxError(RuntimeError):
@@ -280,6 +284,9 @@ def load_library(path=None):
         'dswx_batch_compare': (ctypes.c_int, [vp, vp, ctypes.c_uint32, i64, i64, ctypes.c_double, ctypes.c_double,
                                               ctypes.c_int32, vp, vp]),
         'dswx_compare_host': (ctypes.c_int, [vp, vp, ctypes.c_int32, i64, ctypes.c_double, ctypes.c_double, ctypes.c_int32, vp]),
+        'dswx_histogram_device': (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64, i64, i64, vp, vp]),
+        'dswx_batch_histogram': (ctypes.c_int, [vp, ctypes.c_uint32, i64, i64, ctypes.c_int32, ctypes.c_int32, vp, vp]),
+        'dswx_histogram_host': (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -836,6 +843,13 @@ class Context:
                                             int(bool(equal_nan)), ctypes.c_void_p(out_ptr),
                                             ctypes.c_void_p(stream) if stream else None))
 
+    def histogram_device(self, plane_ptr, kind, n_tiles, n_elems, out_ptr, lo=0, shift=0, tile_stride=0, stream=None):
+        """dswx_histogram_device: one device plane [n_tiles][tile_stride] of one kind (HIST_*; include/dswx_hip.h "histogram",
+        proteus_amd/histogram.py states the definition in numpy) -> device uint64 [n_tiles][256] at out_ptr; asynchronous."""
+        _check(self.lib.dswx_histogram_device(self.handle, ctypes.c_void_p(plane_ptr), int(kind), int(lo), int(shift), int(n_tiles),
+                                              int(n_elems), int(tile_stride), ctypes.c_void_p(out_ptr),
+                                              ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -894,6 +908,17 @@ def compare_host(a, b, atol=0.0, rtol=0.0, equal_nan=True):
     _check(load_library().dswx_compare_host(_host_ptr(a) if a.size else None, _host_ptr(b) if b.size else None, kind_of(a.dtype),
                                             a.size, float(atol), float(rtol), int(bool(equal_nan)), _host_ptr(rec)))
     return rec[0]
+
+
+def histogram_host(a, kind=None, lo=0, shift=0):
+    """dswx_histogram_host (no device needed): the record (uint64 [256]) of a host array, taken in C order, by the library's
+    scalar statement of the definition; the kind follows the dtype when None (name HIST_DIAG for a DIAG plane)."""
+    from .histogram import check
+    a = np.ascontiguousarray(a)
+    kind, lo, shift = check(a.dtype, kind, lo, shift)
+    out = np.zeros(HIST_BINS, dtype=np.uint64)
+    _check(load_library().dswx_histogram_host(_host_ptr(a) if a.size else None, kind, lo, shift, a.size, _host_ptr(out)))
+    return out
 
 
 def cog_layout(height, width, elem_bytes, factors=(), tile=512):
@@ -1082,6 +1107,27 @@ class DeviceBatch:
         out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=RECORD)
         _check(self.ctx.lib.dswx_batch_compare(self.handle, other.handle, mask, int(tile0), int(n_tiles), float(atol), float(rtol),
                                                int(bool(equal_nan)), _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
+        return {n: out[i] for i, n in enumerate(order)}
+
+    def histogram(self, names=None, tile0=0, n_tiles=None, band_lo=0, band_shift=6, stream=None):
+        """dswx_batch_histogram: {name: uint64 [n_tiles, 256]}, the counts of every selected plane of tiles tile0 .. tile0 +
+        n_tiles - 1 (default: every plane the batch has and every tile from tile0), by ONE kernel launch; complete on return.
+        The bands are binned linearly with band_lo / band_shift (the defaults: reflectances 0 .. 16383 in bins of 64), 'diag' by
+        its five test bits, every other plane by its byte: proteus_amd.histogram.histogram(read_tile(name, t), kind, lo, shift)
+        is the same record."""
+        names = self.plane_names() if names is None else list(names)
+        mask = 0
+        for n in names:
+            if n not in PLANE_INDEX:
+                raise ValueError(f'unknown plane {n!r}')
+            mask |= 1 << PLANE_INDEX[n]
+        if n_tiles is None:
+            n_tiles = BATCH_ALL_TILES
+        count = self.n_tiles - tile0 if n_tiles == BATCH_ALL_TILES else n_tiles
+        order = sorted(set(names), key=PLANE_INDEX.get)
+        out = np.zeros((len(order), max(int(count), 0), HIST_BINS), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_histogram(self.handle, mask, int(tile0), int(n_tiles), int(band_lo), int(band_shift),
+                                                 _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
         return {n: out[i] for i, n in enumerate(order)}
 
     def read_tile(self, name, tile):

@@ -383,6 +383,47 @@ int dswx_batch_compare(dswx_batch_t* a, dswx_batch_t* b, uint32_t plane_mask, in
     return DSWX_OK;
 }
 
+// Per-tile histograms of the selected planes (dswx_histogram.hip), one launch; like the checksums the device words live in an
+// allocation of this call's own.  The kind of a plane follows the plane table: int16 planes (the bands) are binned linearly
+// with band_lo / band_shift, DIAG by its five test bits, every other plane by its byte.
+int dswx_batch_histogram(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, int32_t band_lo, int32_t band_shift,
+                         uint64_t* out, void* stream) {
+    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
+    if ((plane_mask >> DSWX_PLANE_COUNTERS) & 1u)
+        return dswx_fail(DSWX_ERR_ARG, "the counters are not histogrammed (three int64 per tile): read them (dswx_batch_planes)");
+    if (int rc = dswx_histogram_check_kind(DSWX_HIST_I16, band_shift)) return rc;
+    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
+    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
+        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
+                         (long long)n_tiles, (long long)b->geom.n_tiles);
+    dswx_histogram_plane planes[DSWX_BATCH_MAX_PLANES];
+    int n_planes = 0;
+    const uint64_t px = (uint64_t)b->geom.height * (uint64_t)b->geom.width, stride = (uint64_t)b->geom.tile_stride;
+    for (int k = 0; k < DSWX_PLANE_COUNTERS; ++k) {
+        if (!((plane_mask >> k) & 1u)) continue;
+        const dswx_plane_desc& d = DSWX_PLANES[k];
+        if (!b->ptr[k]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", k, d.name);
+        const int kind = k == DSWX_PLANE_DIAG ? DSWX_HIST_DIAG : d.kind == DSWX_CMP_I16 ? DSWX_HIST_I16 : DSWX_HIST_U8;
+        static_assert(DSWX_PLANES[DSWX_PLANE_DIAG].kind == DSWX_CMP_U16, "DIAG is a uint16 plane, every plane is 8 or 16 bits wide");
+        planes[n_planes++] = {(const char*)b->ptr[k] + (uint64_t)tile0 * stride * d.bytes, kind, kind == DSWX_HIST_I16 ? band_lo : 0,
+                              kind == DSWX_HIST_I16 ? band_shift : 0, px, stride};
+    }
+    if (n_planes == 0 || n_tiles == 0) return DSWX_OK;
+    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n_planes * (size_t)n_tiles * DSWX_HIST_BINS * sizeof(uint64_t);
+    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
+    uint64_t* dev = nullptr;
+    HIP_TRY(scratch.take(&dev, bytes));
+    if (int rc = dswx_histogram_launch(ctx, planes, n_planes, n_tiles, dev, scratch.s)) return rc;
+    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
+    if (e == hipSuccess) e = scratch.sync();
+    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_histogram: reading the histograms failed: %s", hipGetErrorString(e));
+    return DSWX_OK;
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

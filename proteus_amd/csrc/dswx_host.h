@@ -233,6 +233,19 @@ int dswx_compare_check_tol(double atol, double rtol);
 int dswx_compare_launch(dswx_ctx* ctx, const dswx_compare_pair* pairs, int n_pairs, int64_t n_tiles, double atol, double rtol,
                         int equal_nan, dswx_compare_t* out, hipStream_t s);
 
+// ---- histogram (dswx_histogram.hip): one plane of a launch, in elements of its kind
+struct dswx_histogram_plane {
+    const void* base;
+    int kind;                 // DSWX_HIST_*
+    int lo, shift;            // DSWX_HIST_U16 / DSWX_HIST_I16
+    uint64_t n_elems;         // counted elements of every tile, from its start
+    uint64_t stride_elems;    // between tiles
+};
+int dswx_histogram_elem_bytes(int kind);          // 0: not a kind
+int dswx_histogram_check_kind(int kind, int shift);
+int dswx_histogram_launch(dswx_ctx* ctx, const dswx_histogram_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
+                          hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

@@ -58,6 +58,22 @@ class DevicePlane:
         finally:
             self.engine._give(out)
 
+    def histogram(self, kind=None, lo=0, shift=0):
+        """How many elements of the raster fall into each of 256 bins, as it lies in HBM (dswx_histogram_device;
+        proteus_amd.histogram.histogram of the same array is the same record): uint64 [256] -- a layer of a product run can be
+        counted before it is written, and 2 KiB cross PCIe, not the raster.  The kind follows the dtype when None (uint8 by
+        the byte, uint16 / int16 linearly with lo / shift); name HIST_DIAG for the DIAG layer."""
+        from .histogram import BINS, check
+        kind, lo, shift = check(self.dtype, kind, lo, shift)
+        out = self.engine._take(8 * BINS)
+        try:
+            with self.engine.lock, stages.span('gpu: histogram'):
+                self.engine.ctx.histogram_device(self.ptr, kind, 1, self.nbytes // self.dtype.itemsize, out.ptr, lo=lo, shift=shift)
+                self.engine.ctx.synchronize()
+                return out.download(np.uint64, BINS)
+        finally:
+            self.engine._give(out)
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
