@@ -13,8 +13,12 @@ def main(argv=None):
     ap.add_argument('input_file', type=str, nargs=2, help='Input images')
     ap.add_argument('--device', type=int, default=None, metavar='N',
                     help='compare the bands on GPU N: both files are read into resident planes and only the records cross PCIe')
+    ap.add_argument('--crosstab', action='store_true',
+                    help='also print, for every uint8 band, the table of the values that occur (rows: file 1, columns: file 2) '
+                         'and the share of pixels that agree; computed on the GPU with --device')
     args = ap.parse_args(argv)
-    return 0 if compare_dswx_hls_products(args.input_file[0], args.input_file[1], device=args.device) else 1
+    return 0 if compare_dswx_hls_products(args.input_file[0], args.input_file[1], device=args.device,
+                                          crosstab=args.crosstab) else 1
 
 
 if __name__ == '__main__':

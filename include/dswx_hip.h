@@ -679,6 +679,64 @@ int dswx_batch_histogram(dswx_batch_t* batch, uint32_t plane_mask, int64_t tile0
  * out_u64_256 = uint64_t [DSWX_HIST_BINS], 8-byte aligned. */
 int dswx_histogram_host(const void* data, int32_t kind, int32_t lo, int32_t shift, int64_t n_elems, uint64_t* out_u64_256);
 
+/* ---- crosstab: how the classes of one plane fall into the classes of another, 256 cells per tile (additive to ABI v7) ---
+ * A histogram says how much of each class ONE plane holds; marginals do not determine a joint table, so these entries read
+ * TWO planes in step and count their joint classes -- which WTR-2 classes cloud masking turned into snow or cloud, what a
+ * changed threshold moved between "not water" and "partial surface water", how a band is distributed inside open water and
+ * outside it, the confusion matrix of a product against a validation map -- again without a plane crossing PCIe: 2 KiB per
+ * tile and pair come back.  A C caller tests for them with DSWX_HAS_CROSSTAB.
+ * THE DEFINITION.  A and B are two planes, each [n_tiles][its own tile stride] at its own address; only the first n_elems
+ * elements of a tile are read, the padding up to the stride never.  Plane A is of any histogram kind (a_kind = DSWX_HIST_U8 /
+ * U16 / I16 / DIAG, with a_lo and a_shift as in the histogram section); plane B is always uint8.  col_bits is 0 .. 8: there
+ * are C = 1 << col_bits columns and R = 256 >> col_bits rows.  For the element pair (x, y) = (A[i], B[i]):
+ *   bin = the histogram bin of x exactly as the histogram section defines it (bin < 0: not counted);
+ *   row = row_of_bin[bin], col = col_of_byte[y];
+ *   the pair is counted in cells[row * C + col] iff bin >= 0, row < R and col < C; otherwise it is NOT COUNTED.
+ * One record per tile (and pair) is uint64_t cells[DSWX_CROSSTAB_CELLS]: the 2-KiB record of a histogram.  The counts are
+ * integer sums, so the device entries are deterministic.  It follows that
+ *   - col_bits 0, col_of_byte all zero, row_of_bin the identity: the record IS dswx_histogram's record of A;
+ *   - col_bits 8, row_of_bin all zero, col_of_byte the identity: the U8 histogram of B over the pairs whose A element is counted;
+ *   - where nothing is excluded the row sums are the histogram of row_of_bin[bin(A)], the column sums that of col_of_byte[B]. */
+#define DSWX_HAS_CROSSTAB 1
+#define DSWX_CROSSTAB_CELLS 256
+#define DSWX_CROSSTAB_MAX_PAIRS 6 /* per dswx_batch_crosstab call: the tables ride in the 4 KiB of kernel arguments */
+typedef struct dswx_crosstab_spec {
+    int32_t a_kind;           /* DSWX_HIST_* of plane A */
+    int32_t a_lo, a_shift;    /* DSWX_HIST_U16 / DSWX_HIST_I16 (a shift outside 0 .. 8 is refused for every kind) */
+    int32_t col_bits;         /* 0 .. 8 */
+    uint8_t row_of_bin[256];  /* a value >= 256 >> col_bits: the bin is not counted */
+    uint8_t col_of_byte[256]; /* a value >= 1 << col_bits: the byte is not counted */
+} dswx_crosstab_spec_t;       /* 528 bytes */
+typedef struct dswx_crosstab_pair {
+    int32_t plane_a;          /* DSWX_PLANE_* of batch_a */
+    int32_t plane_b;          /* DSWX_PLANE_* of batch_b: a uint8 plane */
+    dswx_crosstab_spec_t spec;
+} dswx_crosstab_pair_t;       /* 536 bytes */
+/* Planes a [n_tiles][a_stride_elems] and b [n_tiles][b_stride_elems] in DEVICE memory -> out[n_tiles][DSWX_CROSSTAB_CELLS]
+ * (device uint64).  Asynchronous on `stream` (NULL = the context's stream), no synchronisation inside: out is zeroed on the
+ * stream, then one kernel adds into it; the spec's tables travel in the kernel arguments.  A stride of 0 = n_elems; a == b
+ * is legal.  a_kind not a DSWX_HIST_* value, a_shift outside 0 .. 8, col_bits outside 0 .. 8, a NULL spec, a negative size,
+ * tile count or stride, a stride below n_elems, or a NULL plane with n_tiles > 0: DSWX_ERR_ARG; plane a off its element
+ * alignment, or `out` off 8 bytes: DSWX_ERR_ALIGN.  (The arguments are checked before the context is; the limits on the
+ * size of a plane are those of dswx_compare_device.) */
+int dswx_crosstab_device(dswx_ctx_t* ctx, const void* a, const uint8_t* b, const dswx_crosstab_spec_t* spec, int64_t n_tiles,
+                         int64_t n_elems, int64_t a_stride_elems, int64_t b_stride_elems, uint64_t* out_device_u64,
+                         void* stream);
+/* pairs[k].plane_a of batch_a against pairs[k].plane_b of batch_b (batch_a == batch_b is legal: WTR-1 against WTR-2 of one
+ * batch), tiles tile0 .. tile0 + n_tiles - 1 of both (n_tiles DSWX_BATCH_ALL_TILES = up to the last of batch_a), the height x
+ * width pixels of every tile -> out[n_pairs][n_tiles][DSWX_CROSSTAB_CELLS] in HOST memory, complete on return.  ONE kernel
+ * launch for all pairs, on `stream`; at most DSWX_CROSSTAB_MAX_PAIRS pairs, more: DSWX_ERR_ARG.  spec.a_kind must agree with
+ * the library's plane table -- a band takes DSWX_HIST_I16, DIAG takes DSWX_HIST_DIAG or DSWX_HIST_U16, every other plane
+ * DSWX_HIST_U8 -- and plane_b must be a uint8 plane: otherwise DSWX_ERR_ARG, and dswx_last_error() names the plane.  Devices,
+ * tile sizes, tile ranges, missing planes and DSWX_PLANE_COUNTERS: the rules of dswx_batch_compare.  (The device words live
+ * in an allocation made and freed by the call.) */
+int dswx_batch_crosstab(dswx_batch_t* batch_a, dswx_batch_t* batch_b, const dswx_crosstab_pair_t* pairs, int32_t n_pairs,
+                        int64_t tile0, int64_t n_tiles, uint64_t* out_host_u64, void* stream);
+/* The same definition on HOST buffers (any address) in plain scalar C++: needs no device and no context.
+ * out_u64_256 = uint64_t [DSWX_CROSSTAB_CELLS], 8-byte aligned. */
+int dswx_crosstab_host(const void* a, const uint8_t* b, const dswx_crosstab_spec_t* spec, int64_t n_elems,
+                       uint64_t* out_u64_256);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -706,9 +764,9 @@ int dswx_event_destroy(dswx_ctx_t* ctx, void* event);
 int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
-/* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram*
- * call on this context selected (for profiles / DESIGN.md; the histogram's also names its replica count): writes a
- * NUL-terminated string. */
+/* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
+ * dswx_*crosstab* call on this context selected (for profiles / DESIGN.md; the histogram's and the crosstab's also name their
+ * replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 
 #ifdef __cplusplus

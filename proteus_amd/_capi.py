@@ -39,12 +39,15 @@ EXPORTED_SYMBOLS = (
     'dswx_memcpy_h2d_async', 'dswx_memcpy_d2h_async',
     'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host',
     'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host',
-    'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host')
+    'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host',
+    'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
 HIST_U8, HIST_U16, HIST_I16, HIST_DIAG = range(4)
 HIST_BINS = 256
+HAS_CROSSTAB = 1                  # DSWX_HAS_CROSSTAB: additive to ABI v7
+CROSSTAB_CELLS, CROSSTAB_MAX_PAIRS = 256, 6
 
 
 class DswxError(RuntimeError):
@@ -118,6 +121,24 @@ class CompareRecord(ctypes.Structure):
     """dswx_compare_t; proteus_amd.compare.RECORD is the same layout as a numpy dtype."""
     _fields_ = [('n_diff', ctypes.c_int64), ('first', ctypes.c_int64), ('max_abs_diff', ctypes.c_double),
                 ('reserved', ctypes.c_uint64)]
+
+
+class CrosstabSpec(ctypes.Structure):
+    """dswx_crosstab_spec_t; proteus_amd.crosstab.Spec is the Python form."""
+    _fields_ = [('a_kind', ctypes.c_int32), ('a_lo', ctypes.c_int32), ('a_shift', ctypes.c_int32), ('col_bits', ctypes.c_int32),
+                ('row_of_bin', ctypes.c_uint8 * 256), ('col_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.a_kind, spec.a_lo, spec.a_shift, spec.col_bits)
+        ctypes.memmove(c.row_of_bin, spec.row_of_bin.ctypes.data, 256)
+        ctypes.memmove(c.col_of_byte, spec.col_of_byte.ctypes.data, 256)
+        return c
+
+
+class CrosstabPair(ctypes.Structure):
+    """dswx_crosstab_pair_t"""
+    _fields_ = [('plane_a', ctypes.c_int32), ('plane_b', ctypes.c_int32), ('spec', CrosstabSpec)]
 
 
 COG_MAX_LEVELS = 8
@@ -287,6 +308,9 @@ def load_library(path=None):
         'dswx_histogram_device': (ctypes.c_int, [vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64, i64, i64, vp, vp]),
         'dswx_batch_histogram': (ctypes.c_int, [vp, ctypes.c_uint32, i64, i64, ctypes.c_int32, ctypes.c_int32, vp, vp]),
         'dswx_histogram_host': (ctypes.c_int, [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, i64, vp]),
+        'dswx_crosstab_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+        'dswx_batch_crosstab': (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, i64, i64, vp, vp]),
+        'dswx_crosstab_host': (ctypes.c_int, [vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -850,6 +874,14 @@ class Context:
                                               int(n_elems), int(tile_stride), ctypes.c_void_p(out_ptr),
                                               ctypes.c_void_p(stream) if stream else None))
 
+    def crosstab_device(self, a_ptr, b_ptr, spec, n_tiles, n_elems, out_ptr, a_stride=0, b_stride=0, stream=None):
+        """dswx_crosstab_device: device planes a [n_tiles][a_stride] (of spec.a_kind) and b [n_tiles][b_stride] (uint8)
+        cross-tabulated by `spec` (a crosstab.Spec; include/dswx_hip.h "crosstab", proteus_amd/crosstab.py states the
+        definition in numpy) -> device uint64 [n_tiles][256] at out_ptr; asynchronous."""
+        _check(self.lib.dswx_crosstab_device(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
+                                             ctypes.byref(CrosstabSpec.of(spec)), int(n_tiles), int(n_elems), int(a_stride),
+                                             int(b_stride), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -918,6 +950,20 @@ def histogram_host(a, kind=None, lo=0, shift=0):
     kind, lo, shift = check(a.dtype, kind, lo, shift)
     out = np.zeros(HIST_BINS, dtype=np.uint64)
     _check(load_library().dswx_histogram_host(_host_ptr(a) if a.size else None, kind, lo, shift, a.size, _host_ptr(out)))
+    return out
+
+
+def crosstab_host(a, b, spec):
+    """dswx_crosstab_host (no device needed): the record (uint64 [256]) of two host arrays of one shape, taken in C order, by
+    the library's scalar statement of the definition; a of spec.a_kind's dtype, b uint8."""
+    from .histogram import check
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    check(a.dtype, spec.a_kind, spec.a_lo, spec.a_shift)
+    if b.dtype != np.uint8 or a.shape != b.shape:
+        raise ValueError(f'plane b is uint8 of the shape of a: {b.dtype} {b.shape} against {a.shape}')
+    out = np.zeros(CROSSTAB_CELLS, dtype=np.uint64)
+    _check(load_library().dswx_crosstab_host(_host_ptr(a) if a.size else None, _host_ptr(b) if b.size else None,
+                                             ctypes.byref(CrosstabSpec.of(spec)), a.size, _host_ptr(out)))
     return out
 
 
@@ -1129,6 +1175,27 @@ class DeviceBatch:
         _check(self.ctx.lib.dswx_batch_histogram(self.handle, mask, int(tile0), int(n_tiles), int(band_lo), int(band_shift),
                                                  _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
         return {n: out[i] for i, n in enumerate(order)}
+
+    def crosstab(self, pairs, other=None, tile0=0, n_tiles=None, stream=None):
+        """dswx_batch_crosstab: uint64 [n_pairs, n_tiles, 256], for every pair (name_a, name_b, spec) plane name_a of this
+        batch against plane name_b of `other` (default: of this batch) by spec (a crosstab.Spec), tiles tile0 .. tile0 +
+        n_tiles - 1 of both (default: every tile from tile0), by ONE kernel launch for at most CROSSTAB_MAX_PAIRS pairs; complete
+        on return.  proteus_amd.crosstab.crosstab(self.read_tile(name_a, t), other.read_tile(name_b, t), spec) is the same record."""
+        other = self if other is None else other
+        pairs = list(pairs)
+        arr = (CrosstabPair * max(len(pairs), 1))()
+        for k, (name_a, name_b, spec) in enumerate(pairs):
+            for n in (name_a, name_b):
+                if n not in PLANE_INDEX:
+                    raise ValueError(f'unknown plane {n!r}')
+            arr[k].plane_a, arr[k].plane_b, arr[k].spec = PLANE_INDEX[name_a], PLANE_INDEX[name_b], CrosstabSpec.of(spec)
+        if n_tiles is None:
+            n_tiles = BATCH_ALL_TILES
+        count = self.n_tiles - tile0 if n_tiles == BATCH_ALL_TILES else n_tiles
+        out = np.zeros((len(pairs), max(int(count), 0), CROSSTAB_CELLS), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_crosstab(self.handle, other.handle, arr, len(pairs), int(tile0), int(n_tiles),
+                                                _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
+        return out
 
     def read_tile(self, name, tile):
         """Download one plane of one tile as [H,W]."""

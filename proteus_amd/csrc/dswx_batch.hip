@@ -424,6 +424,62 @@ int dswx_batch_histogram(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, in
     return DSWX_OK;
 }
 
+// Plane pairs of two resident batches (or of one) cross-tabulated (dswx_crosstab.hip), one launch; like the checksums the
+// device words live in an allocation of this call's own.  The kind a pair names for its plane a must be the plane table's.
+int dswx_batch_crosstab(dswx_batch_t* a, dswx_batch_t* b, const dswx_crosstab_pair_t* pairs, int32_t n_pairs, int64_t tile0,
+                        int64_t n_tiles, uint64_t* out, void* stream) {
+    if (!a || !b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (n_pairs < 0 || n_pairs > DSWX_CROSSTAB_MAX_PAIRS)
+        return dswx_fail(DSWX_ERR_ARG, "%d pairs: 0 .. %d per call (their tables ride in the kernel arguments)", n_pairs, DSWX_CROSSTAB_MAX_PAIRS);
+    if (n_pairs && !pairs) return dswx_fail(DSWX_ERR_ARG, "pairs is NULL");
+    for (int k = 0; k < n_pairs; ++k)
+        for (const int p : {pairs[k].plane_a, pairs[k].plane_b}) {
+            if (p < 0 || p >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "pair %d names plane %d: not 0 .. %d", k, p, DSWX_BATCH_MAX_PLANES - 1);
+            if (p == DSWX_PLANE_COUNTERS)
+                return dswx_fail(DSWX_ERR_ARG, "the counters are not cross-tabulated (three int64 per tile): read them (dswx_batch_planes)");
+        }
+    if (a->device != b->device) return dswx_fail(DSWX_ERR_ARG, "the batches are on different devices (%d and %d)", a->device, b->device);
+    if (a->geom.height != b->geom.height || a->geom.width != b->geom.width)
+        return dswx_fail(DSWX_ERR_ARG, "the batches differ in tile size: %lld x %lld against %lld x %lld", (long long)a->geom.height,
+                         (long long)a->geom.width, (long long)b->geom.height, (long long)b->geom.width);
+    for (int k = 0; k < n_pairs; ++k)
+        if (int rc = dswx_crosstab_check_spec(&pairs[k].spec)) return rc;
+    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= a->geom.n_tiles) n_tiles = a->geom.n_tiles - tile0;
+    for (const dswx_batch* x : {a, b})
+        if (tile0 < 0 || n_tiles < 0 || tile0 > x->geom.n_tiles || n_tiles > x->geom.n_tiles - tile0)
+            return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside a batch (%lld resident)", (long long)tile0, (long long)n_tiles,
+                             (long long)x->geom.n_tiles);
+    dswx_crosstab_item items[DSWX_CROSSTAB_MAX_PAIRS];
+    const uint64_t px = (uint64_t)a->geom.height * (uint64_t)a->geom.width;
+    const uint64_t sa = (uint64_t)a->geom.tile_stride, sb = (uint64_t)b->geom.tile_stride;
+    for (int k = 0; k < n_pairs; ++k) {
+        const int pa = pairs[k].plane_a, pb = pairs[k].plane_b, kind = pairs[k].spec.a_kind;
+        const dswx_plane_desc& da = DSWX_PLANES[pa];
+        const dswx_plane_desc& db = DSWX_PLANES[pb];
+        if (!a->ptr[pa]) return dswx_fail(DSWX_ERR_ARG, "batch a has no plane %d (%s)", pa, da.name);
+        if (!b->ptr[pb]) return dswx_fail(DSWX_ERR_ARG, "batch b has no plane %d (%s)", pb, db.name);
+        const bool fits = pa == DSWX_PLANE_DIAG ? kind == DSWX_HIST_DIAG || kind == DSWX_HIST_U16
+                          : da.kind == DSWX_CMP_I16 ? kind == DSWX_HIST_I16 : kind == DSWX_HIST_U8;
+        if (!fits) return dswx_fail(DSWX_ERR_ARG, "pair %d: a_kind %d does not bin plane %d (%s), %d bytes per pixel", k, kind, pa, da.name, da.bytes);
+        if (db.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "pair %d: plane b must be a uint8 plane, plane %d (%s) has %d bytes per pixel", k, pb, db.name, db.bytes);
+        items[k] = {(const char*)a->ptr[pa] + (uint64_t)tile0 * sa * da.bytes, (const char*)b->ptr[pb] + (uint64_t)tile0 * sb, &pairs[k].spec,
+                    px, sa, sb};
+    }
+    if (n_pairs == 0 || n_tiles == 0) return DSWX_OK;
+    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
+    dswx_ctx* ctx = a->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n_pairs * (size_t)n_tiles * DSWX_CROSSTAB_CELLS * sizeof(uint64_t);
+    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
+    uint64_t* dev = nullptr;
+    HIP_TRY(scratch.take(&dev, bytes));
+    if (int rc = dswx_crosstab_launch(ctx, items, n_pairs, n_tiles, dev, scratch.s)) return rc;
+    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
+    if (e == hipSuccess) e = scratch.sync();
+    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_crosstab: reading the tables failed: %s", hipGetErrorString(e));
+    return DSWX_OK;
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

@@ -246,6 +246,18 @@ int dswx_histogram_check_kind(int kind, int shift);
 int dswx_histogram_launch(dswx_ctx* ctx, const dswx_histogram_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
                           hipStream_t s);
 
+// ---- crosstab (dswx_crosstab.hip): one plane pair of a launch, a in elements of spec->a_kind, b in bytes
+struct dswx_crosstab_item {
+    const void* a;
+    const void* b;
+    const dswx_crosstab_spec_t* spec;
+    uint64_t n_elems;         // counted pairs of every tile, from its start
+    uint64_t a_stride_elems, b_stride_elems;      // between tiles
+};
+int dswx_crosstab_check_spec(const dswx_crosstab_spec_t* spec);
+int dswx_crosstab_launch(dswx_ctx* ctx, const dswx_crosstab_item* items, int n_pairs, int64_t n_tiles, uint64_t* out,
+                         hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

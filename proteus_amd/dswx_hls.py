@@ -1525,7 +1525,38 @@ def _compare_dswx_hls_metadata(metadata_1, metadata_2):
     return None, True
 
 
-def compare_dswx_hls_products(file_1, file_2, device=None):
+def _crosstab_of_band(band_1, band_2, index=None):
+    """(values of band 1 that occur, values of band 2 that occur, table [len 1, len 2]) of two uint8 rasters -- host arrays
+    (the numpy statement) or DevicePlanes (in HBM; `index`: one band of a [B, H, W] stack); None when the values that occur
+    do not fit the 256 cells."""
+    from . import crosstab as ct
+    on_device = isinstance(band_1, pipeline.DevicePlane)
+    tab = (lambda spec: band_1.crosstab(band_2, spec, index=index)[0]) if on_device else (lambda spec: ct.crosstab(band_1, band_2, spec))
+    # the two marginals first (the reductions of the definition: the histogram of either plane), then the joint table
+    v1 = np.flatnonzero(tab(ct.Spec(col_bits=0, col_of_byte=ct.ZEROS)))
+    v2 = np.flatnonzero(tab(ct.Spec(col_bits=8, row_of_bin=ct.ZEROS)))
+    col_bits = max(len(v2) - 1, 0).bit_length()
+    if len(v1) > 256 >> col_bits:
+        return None
+    spec = ct.Spec(col_bits=col_bits, row_of_bin=ct.classes(v1), col_of_byte=ct.classes(v2))
+    return v1, v2, spec.table(tab(spec))[:len(v1), :len(v2)]
+
+
+def _print_crosstab(description, result):
+    if result is None:
+        print(' ' * 7 + f'     {description}: more values occur than 256 cells hold, no table')
+        return
+    v1, v2, table = result
+    n = int(table.sum())
+    same = int(sum(int(table[i, j]) for i, a in enumerate(v1) for j, b in enumerate(v2) if a == b))
+    print(' ' * 7 + f'     {description}: agreement {same / n if n else float("nan"):.6f} ({same} of {n} pixels)')
+    width = max(8, len(str(n)) + 1)
+    print(' ' * 12 + ' ' * 5 + ''.join(f'{int(v):{width}d}' for v in v2))
+    for i, a in enumerate(v1):
+        print(' ' * 12 + f'{int(a):5d}' + ''.join(f'{int(c):{width}d}' for c in table[i]))
+
+
+def compare_dswx_hls_products(file_1, file_2, device=None, crosstab=False):
     """Band-wise np.allclose(atol=1e-6, equal_nan=True), identical geotransform, identical
     metadata except LICENSE and the keys above (:710-784).  Prints an [OK]/[FAIL] report.
 
@@ -1535,7 +1566,12 @@ def compare_dswx_hls_products(file_1, file_2, device=None):
     at the first difference is fetched, by two element-sized copies.  Same report, with one known difference: for a NaN
     against a number the host path prints no position (its `abs(diff) > tol` scan skips NaN), the device path prints the
     first element that isclose rejects.  (Files of equal shape but different sample types are not compared on the device:
-    GeoTiffError.)"""
+    GeoTiffError.)
+
+    crosstab=True: after the band report, for every uint8 band of equal shape in both files, the table of the values that
+    occur (rows: file 1, columns: file 2) and the share of pixels on which the files agree -- in HBM (dswx_crosstab_device)
+    when a device is given, by the numpy statement (proteus_amd/crosstab.py) otherwise.  The return value and everything
+    printed without the flag stay as they are."""
     for f in (file_1, file_2):
         if not os.path.isfile(f):
             print(f'ERROR file not found: {f}')
@@ -1577,6 +1613,11 @@ def compare_dswx_hls_products(file_1, file_2, device=None):
                     y, x = bad[0]
                     print(' ' * 7 + f'     * input 1 has value "{b1[b][y, x]}" in position (x: {x},'
                           f' y: {y}) whereas input 2 has value "{b2[b][y, x]}" in the same position.')
+        if crosstab:
+            print('Cross-tabulating the uint8 bands (rows: file 1, columns: file 2)...')
+            for b in range(i1.bands):
+                if b1[b].dtype == np.uint8 and b2[b].dtype == np.uint8 and b1[b].shape == b2[b].shape:
+                    _print_crosstab(f'Band {b + 1} - {i1.descriptions[b]}', _crosstab_of_band(b1[b], b2[b]))
     else:
         comparable = p1.shape == p2.shape and p1.dtype == p2.dtype
         if not comparable and p1.shape == p2.shape:
@@ -1590,6 +1631,12 @@ def compare_dswx_hls_products(file_1, file_2, device=None):
                 y, x = divmod(int(rec[b]['first']), i1.width)
                 print(' ' * 7 + f'     * input 1 has value "{p1.element(at)}" in position (x: {x},'
                       f' y: {y}) whereas input 2 has value "{p2.element(at)}" in the same position.')
+        if crosstab:
+            print('Cross-tabulating the uint8 bands (rows: file 1, columns: file 2)...')
+            if comparable and p1.dtype == np.uint8:
+                for b in range(i1.bands):
+                    _print_crosstab(f'Band {b + 1} - {i1.descriptions[b]}',
+                                    _crosstab_of_band(p1, p2, index=b if len(p1.shape) == 3 else None))
         p1.release()
         p2.release()
     same = bool(np.array_equal(i1.geotransform, i2.geotransform))

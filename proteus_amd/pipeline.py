@@ -74,6 +74,34 @@ class DevicePlane:
         finally:
             self.engine._give(out)
 
+    def crosstab(self, other, spec, index=None):
+        """How the classes of this raster fall into the classes of `other` (a uint8 DevicePlane of the same shape) as they lie
+        in HBM (dswx_crosstab_device; proteus_amd.crosstab.crosstab_tiles of the two arrays gives the same records): uint64
+        [n, 256], one record per leading index of a [n, H, W] stack, else one for the raster -- or [1, 256] for the leading
+        index `index` alone; 2 KiB per record cross PCIe, not the rasters.  `spec` is a crosstab.Spec whose a_kind bins this
+        raster's dtype."""
+        from .crosstab import CELLS
+        from .histogram import check
+        check(self.dtype, spec.a_kind, spec.a_lo, spec.a_shift)
+        if self.shape != other.shape or other.dtype != np.uint8:
+            raise ValueError(f'{self.dtype} {self.shape} against {other.dtype} {other.shape}: the other plane is uint8 of the same shape')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        n_elems = self.nbytes // self.dtype.itemsize // max(n_tiles, 1)
+        first = 0
+        if index is not None:
+            if len(self.shape) != 3 or not 0 <= index < n_tiles:
+                raise ValueError(f'index {index} of a raster of shape {self.shape}')
+            first, n_tiles = int(index), 1
+        out = self.engine._take(8 * CELLS * max(n_tiles, 1))
+        try:
+            with self.engine.lock, stages.span('gpu: crosstab'):
+                self.engine.ctx.crosstab_device(self.ptr + first * n_elems * self.dtype.itemsize, other.ptr + first * n_elems,
+                                                spec, n_tiles, n_elems, out.ptr)
+                self.engine.ctx.synchronize()
+                return out.download(np.uint64, CELLS * n_tiles).reshape(n_tiles, CELLS)
+        finally:
+            self.engine._give(out)
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
