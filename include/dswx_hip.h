@@ -737,6 +737,64 @@ int dswx_batch_crosstab(dswx_batch_t* batch_a, dswx_batch_t* batch_b, const dswx
 int dswx_crosstab_host(const void* a, const uint8_t* b, const dswx_crosstab_spec_t* spec, int64_t n_elems,
                        uint64_t* out_u64_256);
 
+/* ---- stack: the tiles of a plane composited per pixel -- counts, latest observation, share (additive to ABI v7) ----------
+ * Checksum, compare, histogram and crosstab reduce WITHIN a tile; these entries reduce ACROSS the tiles of a plane, pixel by
+ * pixel.  When the tiles are the dates of one MGRS tile that is how often a pixel was water out of the times it was observed
+ * at all, its latest clear observation with the clouds filled from earlier dates, and the date that observation came from --
+ * without a WTR plane crossing PCIe: the results are planes in device memory, to be checksummed, histogrammed or written.  A C
+ * caller tests for the entries with DSWX_HAS_STACK.
+ * THE DEFINITION.  A stack is one uint8 plane [n_tiles][tile_stride] at any address; only the first n_elems bytes of a tile
+ * are read, the padding up to the stride never.  The tile index t is time order.  For pixel i, with
+ * c(t) = cat_of_byte[stack[t][i]]:
+ *   count[k][i]    the number of tiles t with c(t) == k, for k < n_cats (a count[k] pointer with k >= n_cats must be NULL);
+ *   n_obs          the sum of count[k][i] over k; t* the largest t with c(t) < n_cats;
+ *   last[i]        stack[t*][i], and last_index[i] = t*; where n_obs == 0 they are `fill` and DSWX_STACK_NONE;
+ *   share[i]       (100 * count[0][i]) / n_obs in integer division (category 0 is the category of interest); where
+ *                  n_obs == 0 it is DSWX_STACK_NO_SHARE.
+ * n_tiles <= DSWX_STACK_MAX_TILES, so a count fits its uint16 and a real index never equals DSWX_STACK_NONE.  n_tiles == 0 is
+ * legal and writes the no-observation values; n_elems == 0 writes nothing.  All of it is integer arithmetic per pixel: the
+ * result is deterministic and independent of the launch geometry. */
+#define DSWX_HAS_STACK 1
+#define DSWX_STACK_MAX_CATS 4
+#define DSWX_STACK_MAX_TILES 65535
+#define DSWX_STACK_NONE 65535          /* last_index of a pixel no tile observed */
+#define DSWX_STACK_NO_SHARE 255        /* share of a pixel no tile observed */
+typedef struct dswx_stack_spec {
+    int32_t n_cats;                    /* 1 .. DSWX_STACK_MAX_CATS */
+    int32_t fill;                      /* 0 .. 255: `last` of a pixel no tile observed */
+    uint8_t cat_of_byte[256];          /* category of a byte; a value >= n_cats: the byte is NOT AN OBSERVATION */
+} dswx_stack_spec_t;                   /* 264 bytes */
+typedef struct dswx_stack_out {        /* planes of n_elems elements each; any pointer may be NULL = not wanted */
+    uint16_t* count[DSWX_STACK_MAX_CATS];
+    uint8_t*  last;
+    uint16_t* last_index;
+    uint8_t*  share;
+} dswx_stack_out_t;
+/* One stack [n_tiles][tile_stride_elems] in DEVICE memory -> the wanted planes of *out_device (device memory, n_elems
+ * elements each).  Asynchronous on `stream` (NULL = the context's stream): ONE kernel launch, no synchronisation, no scratch
+ * of the context.  tile_stride_elems 0 = n_elems.  A NULL spec or out struct, n_cats outside 1 .. 4, fill outside 0 .. 255, a
+ * negative size, tile count or stride, a stride below n_elems, n_tiles > DSWX_STACK_MAX_TILES, a NULL stack with n_tiles > 0
+ * and n_elems > 0, a count[k] pointer with k >= n_cats, or every output NULL: DSWX_ERR_ARG; a count[k] or last_index pointer
+ * off 2 bytes: DSWX_ERR_ALIGN.  The stack and the byte outputs take any address.  (The arguments are checked before the
+ * context is, and a refused call writes nothing; the limits on the size of a plane are those of dswx_compare_device.)
+ * The output planes MUST NOT OVERLAP the stack or each other: that is NOT CHECKED. */
+int dswx_stack_device(dswx_ctx_t* ctx, const uint8_t* stack, const dswx_stack_spec_t* spec, int64_t n_tiles, int64_t n_elems,
+                      int64_t tile_stride_elems, const dswx_stack_out_t* out_device, void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table: Fmask, the masks, every layer but DIAG) of a resident
+ * batch, tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last) as the stack -> the wanted planes
+ * of *out_device: device planes of height x width elements owned by the caller.  Asynchronous on `stream` (NULL = the stream
+ * of the batch's context) like dswx_stack_device.  The address and the stride are those of dswx_batch_planes, so packed,
+ * separate-output, placed, padded and contiguous batches are alike.  A plane that is not uint8 (the bands, DIAG), a plane the
+ * batch does not have, or DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the plane.  Tile ranges: the rules
+ * of dswx_batch_compare. */
+int dswx_batch_stack(dswx_batch_t* batch, int32_t plane, const dswx_stack_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                     const dswx_stack_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++: needs no device and no context.  The other half of a comparison,
+ * not a fallback of the two entries above.  The refusals of dswx_stack_device, except that every buffer, the uint16 ones
+ * included, may sit at any address. */
+int dswx_stack_host(const uint8_t* stack, const dswx_stack_spec_t* spec, int64_t n_tiles, int64_t n_elems,
+                    int64_t tile_stride_elems, const dswx_stack_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -765,8 +823,8 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* call on this context selected (for profiles / DESIGN.md; the histogram's and the crosstab's also name their
- * replica count): writes a NUL-terminated string. */
+ * dswx_*crosstab* / dswx_*stack* call on this context selected (for profiles / DESIGN.md; the histogram's, the crosstab's and
+ * the stack's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 
 #ifdef __cplusplus

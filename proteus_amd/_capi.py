@@ -40,7 +40,8 @@ EXPORTED_SYMBOLS = (
     'dswx_checksum_device', 'dswx_batch_checksum', 'dswx_checksum_host',
     'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host',
     'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host',
-    'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host')
+    'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host',
+    'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -48,6 +49,8 @@ HIST_U8, HIST_U16, HIST_I16, HIST_DIAG = range(4)
 HIST_BINS = 256
 HAS_CROSSTAB = 1                  # DSWX_HAS_CROSSTAB: additive to ABI v7
 CROSSTAB_CELLS, CROSSTAB_MAX_PAIRS = 256, 6
+HAS_STACK = 1                     # DSWX_HAS_STACK: additive to ABI v7
+STACK_MAX_CATS, STACK_MAX_TILES, STACK_NONE, STACK_NO_SHARE = 4, 65535, 65535, 255
 
 
 class DswxError(RuntimeError):
@@ -139,6 +142,31 @@ class CrosstabSpec(ctypes.Structure):
 class CrosstabPair(ctypes.Structure):
     """dswx_crosstab_pair_t"""
     _fields_ = [('plane_a', ctypes.c_int32), ('plane_b', ctypes.c_int32), ('spec', CrosstabSpec)]
+
+
+class StackSpec(ctypes.Structure):
+    """dswx_stack_spec_t; proteus_amd.stack.Spec is the Python form."""
+    _fields_ = [('n_cats', ctypes.c_int32), ('fill', ctypes.c_int32), ('cat_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.n_cats, spec.fill)
+        ctypes.memmove(c.cat_of_byte, spec.cat_of_byte.ctypes.data, 256)
+        return c
+
+
+class StackOut(ctypes.Structure):
+    """dswx_stack_out_t: plane addresses, 0 / None = not wanted."""
+    _fields_ = [('count', ctypes.c_void_p * STACK_MAX_CATS), ('last', ctypes.c_void_p), ('last_index', ctypes.c_void_p),
+                ('share', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, count=(), last=None, last_index=None, share=None):
+        c = cls()
+        for k, p in enumerate(count):
+            c.count[k] = p or None
+        c.last, c.last_index, c.share = last or None, last_index or None, share or None
+        return c
 
 
 COG_MAX_LEVELS = 8
@@ -311,6 +339,9 @@ def load_library(path=None):
         'dswx_crosstab_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_crosstab': (ctypes.c_int, [vp, vp, vp, ctypes.c_int32, i64, i64, vp, vp]),
         'dswx_crosstab_host': (ctypes.c_int, [vp, vp, vp, i64, vp]),
+        'dswx_stack_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
+        'dswx_batch_stack': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
+        'dswx_stack_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -882,6 +913,14 @@ class Context:
                                              ctypes.byref(CrosstabSpec.of(spec)), int(n_tiles), int(n_elems), int(a_stride),
                                              int(b_stride), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None))
 
+    def stack_device(self, stack_ptr, spec, n_tiles, n_elems, out, tile_stride=0, stream=None):
+        """dswx_stack_device: one device stack uint8 [n_tiles][tile_stride] composited per pixel by `spec` (a stack.Spec;
+        include/dswx_hip.h "stack", proteus_amd/stack.py states the definition in numpy) -> the planes `out` names (a StackOut
+        of device addresses, n_elems elements each); one launch, asynchronous."""
+        _check(self.lib.dswx_stack_device(self.handle, ctypes.c_void_p(stack_ptr), ctypes.byref(StackSpec.of(spec)), int(n_tiles),
+                                          int(n_elems), int(tile_stride), ctypes.byref(out),
+                                          ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -965,6 +1004,34 @@ def crosstab_host(a, b, spec):
     _check(load_library().dswx_crosstab_host(_host_ptr(a) if a.size else None, _host_ptr(b) if b.size else None,
                                              ctypes.byref(CrosstabSpec.of(spec)), a.size, _host_ptr(out)))
     return out
+
+
+def stack_host(tiles, spec, want=('count', 'last', 'last_index', 'share')):
+    """dswx_stack_host (no device needed): the planes of proteus_amd.stack.stack_tiles -- those named in `want` -- of a host
+    stack uint8 [n_tiles, ...], by the library's scalar statement of the definition."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != np.uint8 or tiles.ndim < 1:
+        raise ValueError(f'a stack is uint8 [n_tiles, ...], not {tiles.dtype} {tiles.shape}')
+    T, shape = tiles.shape[0], tiles.shape[1:]
+    n = int(np.prod(shape, dtype=np.int64))
+    res = _stack_planes(want, spec, shape, lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = StackOut.of(count=[c.ctypes.data for c in res['count']] if 'count' in res else (),
+                      **{k: res[k].ctypes.data for k in ('last', 'last_index', 'share') if k in res})
+    _check(load_library().dswx_stack_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(StackSpec.of(spec)), T, n, 0,
+                                          ctypes.byref(out)))
+    return res
+
+
+def _stack_planes(want, spec, shape, make):
+    """{name: plane} for the outputs named in `want` ('count' is [n_cats, ...]), each made by make(shape, dtype)."""
+    dtypes = {'count': np.uint16, 'last': np.uint8, 'last_index': np.uint16, 'share': np.uint8}
+    want = tuple(want)
+    for k in want:
+        if k not in dtypes:
+            raise ValueError(f'unknown output {k!r} (count, last, last_index, share)')
+    if not want:
+        raise ValueError('no output wanted')
+    return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
 
 
 def cog_layout(height, width, elem_bytes, factors=(), tile=512):
@@ -1196,6 +1263,28 @@ class DeviceBatch:
         _check(self.ctx.lib.dswx_batch_crosstab(self.handle, other.handle, arr, len(pairs), int(tile0), int(n_tiles),
                                                 _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
         return out
+
+    def stack(self, name, spec, tile0=0, n_tiles=None, want=('count', 'last', 'last_index', 'share'), stream=None):
+        """dswx_batch_stack: tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of the uint8 plane `name`
+        composited per pixel by `spec` (a stack.Spec), by ONE kernel launch, asynchronous on `stream`.  Returns {output:
+        DeviceBuffer} for the outputs named in `want`: 'count' uint16 [n_cats][H*W], 'last' uint8 [H*W], 'last_index' uint16
+        [H*W], 'share' uint8 [H*W] -- device planes owned by the caller.  proteus_amd.stack.stack_tiles of the downloaded
+        tiles gives the same planes."""
+        if name not in PLANE_INDEX:
+            raise ValueError(f'unknown plane {name!r}')
+        n = max(self.n_pixels, 1)
+        res = _stack_planes(want, spec, (n,), lambda shp, dt: self.ctx.malloc(int(np.prod(shp)) * np.dtype(dt).itemsize))
+        out = StackOut.of(count=[res['count'].ptr + 2 * n * k for k in range(spec.n_cats)] if 'count' in res else (),
+                          **{k: res[k].ptr for k in ('last', 'last_index', 'share') if k in res})
+        try:
+            _check(self.ctx.lib.dswx_batch_stack(self.handle, PLANE_INDEX[name], ctypes.byref(StackSpec.of(spec)), int(tile0),
+                                                 int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
+                                                 ctypes.c_void_p(stream) if stream else None))
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
 
     def read_tile(self, name, tile):
         """Download one plane of one tile as [H,W]."""

@@ -258,6 +258,13 @@ int dswx_crosstab_check_spec(const dswx_crosstab_spec_t* spec);
 int dswx_crosstab_launch(dswx_ctx* ctx, const dswx_crosstab_item* items, int n_pairs, int64_t n_tiles, uint64_t* out,
                          hipStream_t s);
 
+// ---- stack (dswx_stack.hip): the shared checks of the entries (resolves a stride of 0; `align`: the uint16 outputs must be
+// 2-byte aligned), and the one launch for arguments that passed them
+int dswx_stack_check(const uint8_t* stack, const dswx_stack_spec_t* spec, int64_t n_tiles, int64_t n_elems, int64_t* stride,
+                     const dswx_stack_out_t* out, bool align);
+int dswx_stack_launch(dswx_ctx* ctx, const uint8_t* stack, const dswx_stack_spec_t* spec, int64_t n_tiles, int64_t n_elems,
+                      int64_t stride, const dswx_stack_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

@@ -102,6 +102,26 @@ class DevicePlane:
         finally:
             self.engine._give(out)
 
+    def stack(self, spec, want=('count', 'last', 'last_index', 'share')):
+        """The rasters of a [n, H, W] uint8 stack composited per pixel as they lie in HBM (dswx_stack_device;
+        proteus_amd.stack.stack_tiles of the same array gives the same planes): a dict of [H, W] DevicePlanes for the outputs
+        named in `want` -- 'count' gives 'count0' .. 'count<n_cats - 1>' (uint16), then 'last' (uint8), 'last_index' (uint16)
+        and 'share' (uint8) -- which stay on the device, each to be checksummed, histogrammed or written.  `spec` is a
+        stack.Spec (stack.wtr_spec for a WTR layer)."""
+        if len(self.shape) != 3 or self.dtype != np.uint8:
+            raise ValueError(f'a stack is a uint8 [n, H, W] plane, not {self.dtype} {self.shape}')
+        n_tiles, shape = self.shape[0], self.shape[1:]
+        made = _capi._stack_planes(want, spec, shape, lambda shp, dt: [self.engine.plane(shape, dt) for _ in range(shp[0])]
+                                   if len(shp) == 3 else self.engine.plane(shp, dt))
+        out = _capi.StackOut.of(count=[p.ptr for p in made.get('count', ())],
+                                **{k: made[k].ptr for k in ('last', 'last_index', 'share') if k in made})
+        with self.engine.lock, stages.span('gpu: stack'):
+            self.engine.ctx.stack_device(self.ptr, spec, n_tiles, shape[0] * shape[1], out)
+            self.engine.ctx.synchronize()
+        res = {f'count{k}': p for k, p in enumerate(made.pop('count', ()))}
+        res.update(made)
+        return res
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
