@@ -211,14 +211,17 @@ def get_binary_representation(diag_decimal, nbits=6):
 # A9  _apply_aerosol_class_remapping :1249-1302 (+ _single_class :1210-1246)
 # ---------------------------------------------------------------------------
 def apply_aerosol_class_remapping(wtr_1, nir, preliminary_cloud, fmask,
-                                  fmask_values_by_class=None):
-    """In place on wtr_1 and preliminary_cloud, classes visited 0, 2, 3, 4."""
+                                  fmask_values_by_class=None, max_nir=None):
+    """In place on wtr_1 and preliminary_cloud, classes visited 0, 2, 3, 4.  max_nir: another value for the reference's
+    constant AEROSOL_REMAPPING_MAX_NIR (tests of the C-ABI's aerosol_max_nir)."""
     if fmask_values_by_class is None:
         fmask_values_by_class = DEFAULT_AEROSOL_FMASK_VALUES
+    if max_nir is None:
+        max_nir = AEROSOL_MAX_NIR
     for in_class in (0, 2, 3, 4):
         remap = (np.isin(fmask, fmask_values_by_class[in_class]) &
                  (wtr_1 == in_class) &
-                 (nir <= AEROSOL_MAX_NIR))
+                 (nir <= max_nir))
         wtr_1[remap] = 1
         sel = np.where(remap & (preliminary_cloud != FILL_U8))
         preliminary_cloud[sel] = np.bitwise_or(preliminary_cloud[sel], 8)
@@ -340,7 +343,8 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
                   clip_negative_reflectance=True,
                   mask_adjacent_to_cloud_mode='mask',
                   apply_aerosol=True, aerosol_fmask_values=None,
-                  collapse=True, with_indices=False, offset_and_scale=None, binary_dilation=None):
+                  collapse=True, with_indices=False, offset_and_scale=None, binary_dilation=None,
+                  aerosol_max_nir=None):
     """Run the whole per-pixel chain on one tile, in the reference's order.
 
     `bands` are the RAW int16 planes as read from file (fill values still in
@@ -348,7 +352,8 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
     when `collapse` is True (WTR, WTR-1, WTR-2 collapsed at save time,
     :2688-2689), or in the in-memory uncollapsed form otherwise, plus
     `WTR-1-AEROSOL` (the in-place remapped WTR-1 that feeds WTR-2, and that the
-    multi-band output file receives, :5381-5396) and `counters`.  `binary_dilation`: see add_snow_to_cloud_layer.
+    multi-band output file receives, :5381-5396) and `counters`.  `binary_dilation`: see add_snow_to_cloud_layer;
+    `aerosol_max_nir`: see apply_aerosol_class_remapping.
     """
     if thr is None:
         thr = Thresholds()
@@ -370,7 +375,7 @@ def classify_tile(bands, fmask, thr=None, *, landcover=None, shadow=None,
     wtr_1_saved = wtr_1.copy()                                     # saved at :5251
     if apply_aerosol:
         apply_aerosol_class_remapping(wtr_1, nir, cloud, fmask,
-                                      aerosol_fmask_values)        # :5261
+                                      aerosol_fmask_values, aerosol_max_nir)   # :5261
     wtr_2 = apply_landcover_and_shadow_masks(wtr_1, nir, landcover, shadow,
                                              thr)                  # :5268
     cloud = add_snow_to_cloud_layer(wtr_2, cloud, fmask,
