@@ -795,6 +795,72 @@ int dswx_batch_stack(dswx_batch_t* batch, int32_t plane, const dswx_stack_spec_t
 int dswx_stack_host(const uint8_t* stack, const dswx_stack_spec_t* spec, int64_t n_tiles, int64_t n_elems,
                     int64_t tile_stride_elems, const dswx_stack_out_t* out_host);
 
+/* ---- grid: a plane aggregated onto a coarse grid -- per-cell category counts, share, coverage, majority (additive to ABI v7)
+ * Checksum, compare, histogram and crosstab reduce a tile as a flat run of elements and stack reduces across tiles; none of
+ * them knows that a tile is a height x width raster.  These entries do: they aggregate every tile onto cells of cell_h x
+ * cell_w pixels -- the water fraction of 900 m cells of a 30 m WTR layer, the fraction of each cell that was observed at all,
+ * and a majority overview that keeps class bytes legal without throwing pixels away -- without the plane crossing PCIe.  The
+ * results are small planes in device memory, [n_tiles][GH * GW], to be histogrammed, cross-tabulated, stacked or written.  A C
+ * caller tests for the entries with DSWX_HAS_GRID.
+ * THE DEFINITION.  A plane is uint8 [n_tiles][tile_stride] at any address.  The first height * width bytes of a tile are its
+ * raster, rows contiguous with a row pitch of `width`; the padding up to the stride is never read.  The grid has
+ * GH = ceil(height / cell_h) rows and GW = ceil(width / cell_w) columns of cells; cell (gy, gx) covers the rows gy * cell_h ..
+ * min(height, (gy + 1) * cell_h) - 1 and the columns gx * cell_w .. min(width, (gx + 1) * cell_w) - 1, so the last row and the
+ * last column of cells are ragged, and n_pix is the number of pixels a cell really covers.  For every tile and cell, with
+ * c(p) = cat_of_byte[byte at pixel p] (the table of a stack spec, unchanged):
+ *   count[k]   the number of pixels p of the cell with c(p) == k, for k < n_cats (a count[k] pointer with k >= n_cats must be
+ *              NULL);
+ *   n_obs      the sum of count[k] over k;
+ *   share      (100 * count[0]) / n_obs in integer division (category 0 is the category of interest); DSWX_GRID_NO_SHARE
+ *              where n_obs == 0;
+ *   coverage   (100 * n_obs) / n_pix in integer division: 0 .. 100;
+ *   major      the smallest k whose count is the largest; DSWX_GRID_NONE where n_obs == 0.
+ * min(cell_h, height) * min(cell_w, width) <= DSWX_GRID_MAX_CELL_PIXELS, so 100 * count fits 32 bits and a whole 3660 x 3660
+ * tile may be ONE cell (for one cell per tile dswx_batch_histogram gives the same counts faster: a cell belongs to one
+ * workgroup here).  n_tiles == 0 or an empty raster writes nothing.  All of it is integer arithmetic: the result is
+ * deterministic and independent of the launch geometry. */
+#define DSWX_HAS_GRID 1
+#define DSWX_GRID_MAX_CATS 4
+#define DSWX_GRID_MAX_CELL_PIXELS (1 << 24)
+#define DSWX_GRID_NO_SHARE 255         /* share of a cell without an observation */
+#define DSWX_GRID_NONE 255             /* major of a cell without an observation */
+typedef struct dswx_grid_spec {
+    int32_t n_cats;                    /* 1 .. DSWX_GRID_MAX_CATS */
+    int32_t cell_h, cell_w;            /* >= 1 */
+    uint8_t cat_of_byte[256];          /* category of a byte; a value >= n_cats: the byte is NOT AN OBSERVATION */
+} dswx_grid_spec_t;                    /* 268 bytes */
+typedef struct dswx_grid_out {         /* planes [n_tiles][GH * GW], dense; any pointer may be NULL = not wanted */
+    uint32_t* count[DSWX_GRID_MAX_CATS];
+    uint8_t*  share;
+    uint8_t*  coverage;
+    uint8_t*  major;
+} dswx_grid_out_t;
+/* One plane [n_tiles][tile_stride_elems] in DEVICE memory -> the wanted planes of *out_device (device memory, n_tiles x GH x
+ * GW elements each).  Asynchronous on `stream` (NULL = the context's stream): ONE kernel launch, no synchronisation, no scratch
+ * of the context, nothing zeroed in front.  tile_stride_elems 0 = height * width.  A NULL spec or out struct, n_cats outside
+ * 1 .. 4, a cell size below 1, a cell of more than DSWX_GRID_MAX_CELL_PIXELS pixels, a negative size, tile count or stride, a
+ * stride below height * width, a NULL plane with something to read, a count[k] pointer with k >= n_cats, or every output
+ * NULL: DSWX_ERR_ARG; a count[k] pointer off 4 bytes: DSWX_ERR_ALIGN.  The plane and the byte outputs take any address.  (The
+ * arguments are checked before the context is, and a refused call writes nothing; height and width are at most 2^30, the
+ * limits on the size of a plane are those of dswx_compare_device.)  The output planes MUST NOT OVERLAP the plane or each
+ * other: that is NOT CHECKED. */
+int dswx_grid_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height,
+                     int64_t width, int64_t tile_stride_elems, const dswx_grid_out_t* out_device, void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table: Fmask, the masks, every layer but DIAG) of a resident
+ * batch, tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last) -> the wanted planes of
+ * *out_device: device planes of n_tiles x GH x GW elements owned by the caller, output tile 0 = tile0.  Asynchronous on
+ * `stream` (NULL = the stream of the batch's context) like dswx_grid_device.  The address and the stride are those of
+ * dswx_batch_planes, so packed, separate-output, placed, padded and contiguous batches are alike.  A plane that is not uint8
+ * (the bands, DIAG), a plane the batch does not have, or DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the
+ * plane.  Tile ranges: the rules of dswx_batch_compare. */
+int dswx_batch_grid(dswx_batch_t* batch, int32_t plane, const dswx_grid_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                    const dswx_grid_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++: needs no device and no context.  The other half of a comparison,
+ * not a fallback of the two entries above.  The refusals of dswx_grid_device, except that every buffer, the uint32 ones
+ * included, may sit at any address. */
+int dswx_grid_host(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                   int64_t tile_stride_elems, const dswx_grid_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -823,8 +889,8 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* call on this context selected (for profiles / DESIGN.md; the histogram's, the crosstab's and
- * the stack's also name their replica count): writes a NUL-terminated string. */
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* call on this context selected (for profiles / DESIGN.md; the histogram's, the
+ * crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 
 #ifdef __cplusplus

@@ -41,7 +41,8 @@ EXPORTED_SYMBOLS = (
     'dswx_compare_device', 'dswx_batch_compare', 'dswx_compare_host',
     'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host',
     'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host',
-    'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host')
+    'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host',
+    'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -51,6 +52,8 @@ HAS_CROSSTAB = 1                  # DSWX_HAS_CROSSTAB: additive to ABI v7
 CROSSTAB_CELLS, CROSSTAB_MAX_PAIRS = 256, 6
 HAS_STACK = 1                     # DSWX_HAS_STACK: additive to ABI v7
 STACK_MAX_CATS, STACK_MAX_TILES, STACK_NONE, STACK_NO_SHARE = 4, 65535, 65535, 255
+HAS_GRID = 1                      # DSWX_HAS_GRID: additive to ABI v7
+GRID_MAX_CATS, GRID_MAX_CELL_PIXELS, GRID_NO_SHARE, GRID_NONE = 4, 1 << 24, 255, 255
 
 
 class DswxError(RuntimeError):
@@ -166,6 +169,32 @@ class StackOut(ctypes.Structure):
         for k, p in enumerate(count):
             c.count[k] = p or None
         c.last, c.last_index, c.share = last or None, last_index or None, share or None
+        return c
+
+
+class GridSpec(ctypes.Structure):
+    """dswx_grid_spec_t; proteus_amd.grid.Spec is the Python form."""
+    _fields_ = [('n_cats', ctypes.c_int32), ('cell_h', ctypes.c_int32), ('cell_w', ctypes.c_int32),
+                ('cat_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.n_cats, spec.cell_h, spec.cell_w)
+        ctypes.memmove(c.cat_of_byte, spec.cat_of_byte.ctypes.data, 256)
+        return c
+
+
+class GridOut(ctypes.Structure):
+    """dswx_grid_out_t: plane addresses, 0 / None = not wanted."""
+    _fields_ = [('count', ctypes.c_void_p * GRID_MAX_CATS), ('share', ctypes.c_void_p), ('coverage', ctypes.c_void_p),
+                ('major', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, count=(), share=None, coverage=None, major=None):
+        c = cls()
+        for k, p in enumerate(count):
+            c.count[k] = p or None
+        c.share, c.coverage, c.major = share or None, coverage or None, major or None
         return c
 
 
@@ -342,6 +371,9 @@ def load_library(path=None):
         'dswx_stack_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
         'dswx_batch_stack': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_stack_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp]),
+        'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+        'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
+        'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -921,6 +953,14 @@ class Context:
                                           int(n_elems), int(tile_stride), ctypes.byref(out),
                                           ctypes.c_void_p(stream) if stream else None))
 
+    def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
+        """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
+        onto cells by `spec` (a grid.Spec; include/dswx_hip.h "grid", proteus_amd/grid.py states the definition in numpy) ->
+        the planes `out` names (a GridOut of device addresses, n_tiles x GH x GW elements each); one launch, asynchronous."""
+        _check(self.lib.dswx_grid_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(GridSpec.of(spec)), int(n_tiles),
+                                         int(height), int(width), int(tile_stride), ctypes.byref(out),
+                                         ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -1029,6 +1069,38 @@ def _stack_planes(want, spec, shape, make):
     for k in want:
         if k not in dtypes:
             raise ValueError(f'unknown output {k!r} (count, last, last_index, share)')
+    if not want:
+        raise ValueError('no output wanted')
+    return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
+
+
+def grid_host(tiles, spec, want=('count', 'share', 'coverage', 'major'), raster=None):
+    """dswx_grid_host (no device needed): the planes of proteus_amd.grid.grid_tiles -- those named in `want` -- of a host
+    plane uint8 [n_tiles, H, W], by the library's scalar statement of the definition.  With raster=(H, W), `tiles` is a padded
+    plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
+    if raster is None:
+        (n, H, W), stride = tiles.shape, 0
+    else:
+        (n, stride), (H, W) = tiles.shape, raster
+    from .grid import grid_shape
+    res = _grid_planes(want, spec, (n,) + grid_shape(H, W, spec), lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = GridOut.of(count=[c.ctypes.data for c in res['count']] if 'count' in res else (),
+                     **{k: res[k].ctypes.data for k in ('share', 'coverage', 'major') if k in res})
+    _check(load_library().dswx_grid_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(GridSpec.of(spec)), n, H, W,
+                                         stride, ctypes.byref(out)))
+    return res
+
+
+def _grid_planes(want, spec, shape, make):
+    """{name: plane} for the outputs named in `want` ('count' is [n_cats, ...]), each made by make(shape, dtype)."""
+    dtypes = {'count': np.uint32, 'share': np.uint8, 'coverage': np.uint8, 'major': np.uint8}
+    want = tuple(want)
+    for k in want:
+        if k not in dtypes:
+            raise ValueError(f'unknown output {k!r} (count, share, coverage, major)')
     if not want:
         raise ValueError('no output wanted')
     return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
@@ -1280,6 +1352,33 @@ class DeviceBatch:
             _check(self.ctx.lib.dswx_batch_stack(self.handle, PLANE_INDEX[name], ctypes.byref(StackSpec.of(spec)), int(tile0),
                                                  int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
                                                  ctypes.c_void_p(stream) if stream else None))
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
+
+    def grid(self, name, spec, tile0=0, n_tiles=None, want=('count', 'share', 'coverage', 'major'), stream=None):
+        """dswx_batch_grid: tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of the uint8 plane `name`
+        aggregated onto cells by `spec` (a grid.Spec), by ONE kernel launch, asynchronous on `stream`.  Returns {output:
+        DeviceBuffer} for the outputs named in `want`: 'count' uint32 [n_cats][n_tiles][GH*GW], 'share', 'coverage' and
+        'major' uint8 [n_tiles][GH*GW] -- device planes owned by the caller.  proteus_amd.grid.grid_tiles of the downloaded
+        tiles gives the same planes."""
+        if name not in PLANE_INDEX:
+            raise ValueError(f'unknown plane {name!r}')
+        from .grid import grid_shape
+        if n_tiles == BATCH_ALL_TILES:
+            n_tiles = None
+        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        gh, gw = grid_shape(self.height, self.width, spec)
+        n = max(nt * gh * gw, 1)
+        res = _grid_planes(want, spec, (n,), lambda shp, dt: self.ctx.malloc(int(np.prod(shp)) * np.dtype(dt).itemsize))
+        out = GridOut.of(count=[res['count'].ptr + 4 * n * k for k in range(spec.n_cats)] if 'count' in res else (),
+                         **{k: res[k].ptr for k in ('share', 'coverage', 'major') if k in res})
+        try:
+            _check(self.ctx.lib.dswx_batch_grid(self.handle, PLANE_INDEX[name], ctypes.byref(GridSpec.of(spec)), int(tile0),
+                                                int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
+                                                ctypes.c_void_p(stream) if stream else None))
         except DswxError:
             for buf in res.values():
                 buf.free()

@@ -122,6 +122,29 @@ class DevicePlane:
         res.update(made)
         return res
 
+    def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
+        """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;
+        proteus_amd.grid.grid_tiles of the same array gives the same planes): a dict of [n, GH, GW] DevicePlanes for the
+        outputs named in `want` -- 'count' gives 'count0' .. 'count<n_cats - 1>' (uint32), then 'share', 'coverage' and
+        'major' (uint8) -- which stay on the device, each to be histogrammed, stacked or written.  `spec` is a grid.Spec
+        (grid.wtr_grid_spec for a WTR layer)."""
+        from .grid import grid_shape
+        if len(self.shape) not in (2, 3) or self.dtype != np.uint8:
+            raise ValueError(f'a grid is made of a uint8 [n, H, W] or [H, W] plane, not {self.dtype} {self.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        shape = (n_tiles,) + grid_shape(height, width, spec)
+        made = _capi._grid_planes(want, spec, shape, lambda shp, dt: [self.engine.plane(shape, dt) for _ in range(shp[0])]
+                                  if len(shp) == 4 else self.engine.plane(shp, dt))
+        out = _capi.GridOut.of(count=[p.ptr for p in made.get('count', ())],
+                               **{k: made[k].ptr for k in ('share', 'coverage', 'major') if k in made})
+        with self.engine.lock, stages.span('gpu: grid'):
+            self.engine.ctx.grid_device(self.ptr, spec, n_tiles, height, width, out)
+            self.engine.ctx.synchronize()
+        res = {f'count{k}': p for k, p in enumerate(made.pop('count', ()))}
+        res.update(made)
+        return res
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
