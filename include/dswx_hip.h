@@ -861,6 +861,72 @@ int dswx_batch_grid(dswx_batch_t* batch, int32_t plane, const dswx_grid_spec_t* 
 int dswx_grid_host(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                    int64_t tile_stride_elems, const dswx_grid_out_t* out_host);
 
+/* ---- label: the connected bodies of a plane -- per-pixel label and body size, a sieved copy, a summary (additive to ABI v7)
+ * Every entry above treats a pixel on its own or in a fixed rectangle.  A surface-water product is about water BODIES: how
+ * many lakes a tile holds, how large each is, which one-pixel specks are noise.  These entries label the connected bodies of
+ * every tile of a plane without the plane crossing PCIe; the results are planes in device memory that dswx_histogram_device,
+ * dswx_checksum_device and dswx_grid_device accept.  A C caller tests for the entries with DSWX_HAS_LABEL.
+ * THE DEFINITION.  A plane is uint8 [n_tiles][tile_stride] at any address.  The first height * width bytes of a tile are its
+ * raster, rows contiguous with a row pitch of `width`; the padding up to the stride is never read.  Pixel p is a MEMBER iff
+ * member_of_byte[byte at p] != 0.  Two members are ADJACENT when they are neighbours in the 4-neighbourhood (connectivity 4)
+ * or the 8-neighbourhood (connectivity 8) of the same tile; rows do not wrap -- (y, width - 1) and (y + 1, 0) are not
+ * neighbours -- and tiles never connect.  A BODY is a maximal set of members connected through adjacency.  Per tile, with
+ * idx(p) = y * width + x:
+ *   label[p]    uint32: 0 for a non-member, else 1 + the smallest idx(q) over the body of p.  This is the order in which
+ *               scipy.ndimage.label numbers bodies WITHOUT the renumbering to 1 .. K: renumbering is deliberately not done
+ *               here (the labels of a tile are distinct and ordered, not dense);
+ *   size[p]     uint32: 0 for a non-member, else the number of pixels of the body of p;
+ *   sieved[p]   uint8: the input byte, except that a member whose body has fewer than min_size pixels becomes `replace`;
+ *               min_size == 1 copies.  (GDAL's sieve lets a removed body adopt the value of its largest neighbour; this rule
+ *               is simpler: one replacement byte);
+ *   summary     uint64 [DSWX_LABEL_SUMMARY_WORDS] per tile: word 0 bodies; 1 member pixels; 2 the largest size; 3 the label of
+ *               the largest body (the smallest label on a tie, 0 when there is none); 4 bodies with size >= min_size; 5 the
+ *               pixels in those bodies; 6, 7 zero; 8 + b, b = 0 .. 31, the bodies with floor(log2(size)) == b.
+ * height * width <= 2^31, so that a label fits 32 bits.  n_tiles == 0 or an empty raster writes nothing.  All of it is
+ * integer arithmetic: the result is deterministic and independent of the launch geometry and of the order in which atomics
+ * arrive. */
+#define DSWX_HAS_LABEL 1
+#define DSWX_LABEL_SUMMARY_WORDS 40
+typedef struct dswx_label_spec {
+    int32_t connectivity;              /* 4 or 8 */
+    int32_t replace;                   /* 0 .. 255: the byte of a sieved-out member */
+    uint32_t min_size;                 /* >= 1 */
+    uint8_t member_of_byte[256];       /* != 0: a pixel with this byte is a member */
+} dswx_label_spec_t;                   /* 268 bytes */
+typedef struct dswx_label_out {        /* planes [n_tiles][height * width], dense; summary [n_tiles][40] */
+    uint32_t* label;                   /* REQUIRED: it is the working array of the union-find */
+    uint32_t* size;                    /* required whenever sieved or summary is wanted; else NULL = not wanted */
+    uint8_t*  sieved;                  /* NULL = not wanted */
+    uint64_t* summary;                 /* NULL = not wanted */
+} dswx_label_out_t;
+/* One plane [n_tiles][tile_stride_elems] in DEVICE memory -> the wanted planes of *out_device (device memory).  Asynchronous
+ * on `stream` (NULL = the context's stream): at most five kernel launches (label a rectangle in LDS; unite across the seams of
+ * the rectangles; flatten and count; broadcast the sizes, sieve and summarise; unpack the summary's largest-body key) plus one
+ * hipMemsetAsync of `summary`; no synchronisation, no scratch of the context, no allocation, and nothing the caller has to
+ * zero in front: a second call on the same outputs gives the same result.  No workgroup ever waits for another.
+ * tile_stride_elems 0 = height * width.  A NULL spec or out struct, a connectivity that is not 4 or 8, `replace` outside
+ * 0 .. 255, min_size == 0, a negative size, tile count or stride, a stride below height * width, height * width above 2^31, a
+ * NULL plane with something to read, a NULL label, or a NULL size with sieved or summary wanted: DSWX_ERR_ARG; label or size
+ * off 4 bytes or summary off 8: DSWX_ERR_ALIGN.  The plane and `sieved` take any address.  (The arguments are checked before
+ * the context is, and a refused call writes nothing; the limits on the size of a plane are those of dswx_compare_device.)
+ * The outputs MUST NOT OVERLAP the plane or each other: that is NOT CHECKED. */
+int dswx_label_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height,
+                      int64_t width, int64_t tile_stride_elems, const dswx_label_out_t* out_device, void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table: Fmask, the masks, every layer but DIAG) of a resident
+ * batch, tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last) -> the wanted planes of
+ * *out_device: device planes owned by the caller, output tile 0 = tile0.  Asynchronous on `stream` (NULL = the stream of the
+ * batch's context) like dswx_label_device.  The address and the stride are those of dswx_batch_planes, so packed,
+ * separate-output, placed, padded and contiguous batches are alike.  A plane that is not uint8 (the bands, DIAG), a plane the
+ * batch does not have, or DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the plane.  Tile ranges: the rules
+ * of dswx_batch_compare. */
+int dswx_batch_label(dswx_batch_t* batch, int32_t plane, const dswx_label_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                     const dswx_label_out_t* out_device, void* stream);
+/* The same definition on HOST buffers: a plain scalar union-find in C++, needs no device and no context.  The other half of
+ * a comparison, not a fallback of the two entries above.  The refusals of dswx_label_device, except that every buffer, the
+ * uint32 and uint64 ones included, may sit at any address. */
+int dswx_label_host(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                    int64_t tile_stride_elems, const dswx_label_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -889,8 +955,8 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* call on this context selected (for profiles / DESIGN.md; the histogram's, the
- * crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* call on this context selected (for profiles / DESIGN.md; the
+ * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 
 #ifdef __cplusplus

@@ -42,7 +42,8 @@ EXPORTED_SYMBOLS = (
     'dswx_histogram_device', 'dswx_batch_histogram', 'dswx_histogram_host',
     'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host',
     'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host',
-    'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host')
+    'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host',
+    'dswx_label_device', 'dswx_batch_label', 'dswx_label_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -54,6 +55,9 @@ HAS_STACK = 1                     # DSWX_HAS_STACK: additive to ABI v7
 STACK_MAX_CATS, STACK_MAX_TILES, STACK_NONE, STACK_NO_SHARE = 4, 65535, 65535, 255
 HAS_GRID = 1                      # DSWX_HAS_GRID: additive to ABI v7
 GRID_MAX_CATS, GRID_MAX_CELL_PIXELS, GRID_NO_SHARE, GRID_NONE = 4, 1 << 24, 255, 255
+HAS_LABEL = 1                     # DSWX_HAS_LABEL: additive to ABI v7
+LABEL_SUMMARY_WORDS = 40
+LABEL_RECT_H, LABEL_RECT_W = 32, 128   # csrc/dswx_label_rule.h: the rectangle one workgroup labels in LDS (tests build shapes around its seams)
 
 
 class DswxError(RuntimeError):
@@ -196,6 +200,27 @@ class GridOut(ctypes.Structure):
             c.count[k] = p or None
         c.share, c.coverage, c.major = share or None, coverage or None, major or None
         return c
+
+
+class LabelSpec(ctypes.Structure):
+    """dswx_label_spec_t; proteus_amd.label.Spec is the Python form."""
+    _fields_ = [('connectivity', ctypes.c_int32), ('replace', ctypes.c_int32), ('min_size', ctypes.c_uint32),
+                ('member_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.connectivity, spec.replace, spec.min_size)
+        ctypes.memmove(c.member_of_byte, spec.member_of_byte.ctypes.data, 256)
+        return c
+
+
+class LabelOut(ctypes.Structure):
+    """dswx_label_out_t: plane addresses, 0 / None = not wanted."""
+    _fields_ = [('label', ctypes.c_void_p), ('size', ctypes.c_void_p), ('sieved', ctypes.c_void_p), ('summary', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, label=None, size=None, sieved=None, summary=None):
+        return cls(label or None, size or None, sieved or None, summary or None)
 
 
 COG_MAX_LEVELS = 8
@@ -374,6 +399,9 @@ def load_library(path=None):
         'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
+        'dswx_label_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+        'dswx_batch_label': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
+        'dswx_label_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -961,6 +989,14 @@ class Context:
                                          int(height), int(width), int(tile_stride), ctypes.byref(out),
                                          ctypes.c_void_p(stream) if stream else None))
 
+    def label_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
+        """dswx_label_device: the connected bodies of one device plane uint8 [n_tiles][tile_stride], every tile a height x
+        width raster, by `spec` (a label.Spec; include/dswx_hip.h "label", proteus_amd/label.py states the definition in
+        numpy) -> the planes `out` names (a LabelOut of device addresses); a fixed number of launches, asynchronous."""
+        _check(self.lib.dswx_label_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(LabelSpec.of(spec)), int(n_tiles),
+                                          int(height), int(width), int(tile_stride), ctypes.byref(out),
+                                          ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -1104,6 +1140,39 @@ def _grid_planes(want, spec, shape, make):
     if not want:
         raise ValueError('no output wanted')
     return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
+
+
+LABEL_DTYPES = {'label': np.uint32, 'size': np.uint32, 'sieved': np.uint8, 'summary': np.uint64}
+
+
+def _label_wanted(want):
+    """`want` in the order of the struct; 'label' is always made (it is the working array), 'size' with sieved or summary."""
+    want = tuple(want)
+    for k in want:
+        if k not in LABEL_DTYPES:
+            raise ValueError(f'unknown output {k!r} (label, size, sieved, summary)')
+    if not want:
+        raise ValueError('no output wanted')
+    made = {'label'} | set(want) | ({'size'} if 'sieved' in want or 'summary' in want else set())
+    return tuple(k for k in LABEL_DTYPES if k in made)
+
+
+def label_host(tiles, spec, want=('label', 'size', 'sieved', 'summary'), raster=None):
+    """dswx_label_host (no device needed): the planes of proteus_amd.label.label_tiles -- those named in `want`, and the ones
+    they need -- of a host plane uint8 [n_tiles, H, W], by the library's scalar union-find.  With raster=(H, W), `tiles` is a
+    padded plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
+    if raster is None:
+        (n, H, W), stride = tiles.shape, 0
+    else:
+        (n, stride), (H, W) = tiles.shape, raster
+    res = {k: np.zeros((n, LABEL_SUMMARY_WORDS) if k == 'summary' else (n, H, W), dtype=LABEL_DTYPES[k]) for k in _label_wanted(want)}
+    out = LabelOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_label_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(LabelSpec.of(spec)), n, H, W,
+                                          stride, ctypes.byref(out)))
+    return res
 
 
 def cog_layout(height, width, elem_bytes, factors=(), tile=512):
@@ -1379,6 +1448,31 @@ class DeviceBatch:
             _check(self.ctx.lib.dswx_batch_grid(self.handle, PLANE_INDEX[name], ctypes.byref(GridSpec.of(spec)), int(tile0),
                                                 int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
                                                 ctypes.c_void_p(stream) if stream else None))
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
+
+    def label(self, name, spec, tile0=0, n_tiles=None, want=('label', 'size', 'sieved', 'summary'), stream=None):
+        """dswx_batch_label: the connected bodies of tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of
+        the uint8 plane `name` by `spec` (a label.Spec), asynchronous on `stream`.  Returns {output: DeviceBuffer} for the
+        outputs named in `want` and the ones they need ('label' always, 'size' with 'sieved' or 'summary'): 'label' and
+        'size' uint32 [n_tiles][H*W], 'sieved' uint8 [n_tiles][H*W], 'summary' uint64 [n_tiles][40] -- device planes owned by
+        the caller.  proteus_amd.label.label_tiles of the downloaded tiles gives the same planes."""
+        if name not in PLANE_INDEX:
+            raise ValueError(f'unknown plane {name!r}')
+        if n_tiles == BATCH_ALL_TILES:
+            n_tiles = None
+        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        px = self.height * self.width
+        res = {k: self.ctx.malloc(max(nt * (LABEL_SUMMARY_WORDS if k == 'summary' else px), 1) * np.dtype(LABEL_DTYPES[k]).itemsize)
+               for k in _label_wanted(want)}
+        out = LabelOut.of(**{k: b.ptr for k, b in res.items()})
+        try:
+            _check(self.ctx.lib.dswx_batch_label(self.handle, PLANE_INDEX[name], ctypes.byref(LabelSpec.of(spec)), int(tile0),
+                                                 int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
+                                                 ctypes.c_void_p(stream) if stream else None))
         except DswxError:
             for buf in res.values():
                 buf.free()

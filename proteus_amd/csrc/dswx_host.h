@@ -272,6 +272,13 @@ int dswx_grid_check(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t 
 int dswx_grid_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, int64_t stride, const dswx_grid_out_t* out, hipStream_t s);
 
+// ---- label (dswx_label.hip): the shared checks of the entries (resolves a stride of 0; `align`: label and size must be
+// 4-byte and summary 8-byte aligned), and the launches for arguments that passed them
+int dswx_label_check(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                     int64_t* stride, const dswx_label_out_t* out, bool align);
+int dswx_label_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height,
+                      int64_t width, int64_t stride, const dswx_label_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

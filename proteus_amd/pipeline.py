@@ -145,6 +145,25 @@ class DevicePlane:
         res.update(made)
         return res
 
+    def label(self, spec, want=('label', 'size', 'sieved', 'summary')):
+        """The connected bodies of a [n, H, W] (or one [H, W]) uint8 plane as it lies in HBM (dswx_label_device;
+        proteus_amd.label.label_tiles of the same array gives the same planes): a dict of DevicePlanes for the outputs named
+        in `want` and the ones they need ('label' always, 'size' with 'sieved' or 'summary') -- 'label' and 'size' uint32
+        [n, H, W], 'sieved' uint8 [n, H, W], 'summary' uint64 [n, 40] -- which stay on the device: 'sieved' can be
+        histogrammed, gridded or written, every one checksummed.  `spec` is a label.Spec (label.wtr_label_spec for a WTR
+        layer)."""
+        if len(self.shape) not in (2, 3) or self.dtype != np.uint8:
+            raise ValueError(f'bodies are labelled in a uint8 [n, H, W] or [H, W] plane, not {self.dtype} {self.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        made = {k: self.engine.plane((n_tiles, _capi.LABEL_SUMMARY_WORDS) if k == 'summary' else (n_tiles, height, width),
+                                     _capi.LABEL_DTYPES[k]) for k in _capi._label_wanted(want)}
+        out = _capi.LabelOut.of(**{k: p.ptr for k, p in made.items()})
+        with self.engine.lock, stages.span('gpu: label'):
+            self.engine.ctx.label_device(self.ptr, spec, n_tiles, height, width, out)
+            self.engine.ctx.synchronize()
+        return made
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
