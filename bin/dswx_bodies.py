@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`dswx_bodies.py --min-size N [--connectivity 4|8] [--band B] [--no-partial] [--device D] [-o OUTPUT] product.tif`
+"""`dswx_bodies.py --min-size N [--connectivity 4|8] [--band B] [--no-partial] [--device D] [-o OUTPUT] [--table FILE [--max-bodies M]] product.tif`
 
 The water bodies of one layer of a DSWx-HLS product, labelled on the GPU (include/dswx_hip.h "label"): band B (default 1 =
 WTR) of the product file is read into a resident plane; its water pixels (open or, unless --no-partial, partial surface
@@ -9,8 +9,17 @@ summary is printed as one line of JSON: how many bodies, how many water pixels, 
 y * width + x of its first pixel), how many bodies and pixels stay, the bodies per power of two of their size -- and, where
 the file's geotransform gives the size of a pixel, the same areas in square metres.  PROTEUS has no such tool: there is no
 reference output to be equal to; proteus_amd/label.py states what a body is.
+
+With --table FILE the bodies are also tabulated on the GPU (include/dswx_hip.h "body table", proteus_amd/bodies.py) and FILE is
+written as CSV with one line per body KEPT by --min-size, in the order of the bodies' first pixels: rank and label, the first
+pixel, the area in pixels, the bounding box and the centroid in pixels (a pixel's coordinate is its column / row index), the
+perimeter in pixel edges, the open-water and partial-surface-water pixels; and, where the geotransform is known, the area in
+square metres, the perimeter in metres (an edge counted as the mean of the pixel's two sides), the centroid (of pixel
+centres) and the bounding box (of pixel outlines) in map coordinates.  --max-bodies M is the capacity of the table (default:
+the body count of the summary); bodies of rank M and above are not listed.  The JSON line is the same with and without.
 """
 import argparse
+import csv
 import json
 import os
 import sys
@@ -19,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np   # noqa: E402
 
 from proteus_amd import dswx_hls, geotiff, pipeline   # noqa: E402
+from proteus_amd.bodies import ROW_DTYPE, wtr_body_spec   # noqa: E402
 from proteus_amd.label import wtr_label_spec   # noqa: E402
 
 
@@ -41,6 +51,33 @@ def read_band(engine, path, band):
     return plane, info
 
 
+TABLE_COLUMNS = ('rank', 'label', 'first_x', 'first_y', 'area_px', 'x_min', 'x_max', 'y_min', 'y_max', 'centroid_x_px', 'centroid_y_px',
+                 'perimeter_edges', 'open_px', 'partial_px')
+TABLE_MAP_COLUMNS = ('area_m2', 'perimeter_m', 'centroid_map_x', 'centroid_map_y', 'map_x_min', 'map_x_max', 'map_y_min', 'map_y_max')
+
+
+def write_table(path, rows, min_size, width, gt):
+    """The rows (bodies.ROW_DTYPE [n]) of at least min_size pixels -> CSV; `gt` is the geotransform or None."""
+    with open(path, 'w', newline='') as f:
+        w = csv.writer(f)
+        w.writerow(TABLE_COLUMNS + (TABLE_MAP_COLUMNS if gt else ()))
+        for k, r in enumerate(rows):
+            a = int(r['area'])
+            if a < min_size or a == 0:
+                continue
+            first = int(r['label']) - 1
+            x0, x1, y0, y1 = (int(r[c]) for c in ('x_min', 'x_max', 'y_min', 'y_max'))
+            cx, cy, per = int(r['sum_x']) / a, int(r['sum_y']) / a, int(r['perimeter'])
+            line = [k, int(r['label']), first % width, first // width, a, x0, x1, y0, y1, repr(cx), repr(cy), per,
+                    int(r['count'][0]), int(r['count'][1])]
+            if gt:
+                # (north-up files: no rotation terms; a row's y decreases downward, so y_min of the map is the LAST row's lower edge)
+                line += [repr(a * abs(gt[1] * gt[5])), repr(per * (abs(gt[1]) + abs(gt[5])) / 2), repr(gt[0] + (cx + 0.5) * gt[1]),
+                         repr(gt[3] + (cy + 0.5) * gt[5]), repr(gt[0] + x0 * gt[1]), repr(gt[0] + (x1 + 1) * gt[1]),
+                         repr(gt[3] + (y1 + 1) * gt[5]), repr(gt[3] + y0 * gt[5])]
+            w.writerow(line)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description='Label the water bodies of a layer of a product, remove the small ones, summarise')
     ap.add_argument('input_file', type=str, help='DSWx-HLS product file')
@@ -49,6 +86,8 @@ def main(argv=None):
     ap.add_argument('-o', '--output', dest='output', type=str, default=None, help='the sieved layer (default <product>_SIEVED.tif)')
     ap.add_argument('--band', type=int, default=1, metavar='B', help='band of the product file to label (default 1 = WTR)')
     ap.add_argument('--no-partial', action='store_true', help='partial surface water is not water')
+    ap.add_argument('--table', type=str, default=None, metavar='FILE', help='write one CSV line per body kept by --min-size')
+    ap.add_argument('--max-bodies', type=int, default=None, metavar='M', help='capacity of the table (default: the body count)')
     ap.add_argument('--device', type=int, default=None, metavar='D', help='GPU to run on (default $DSWX_DEVICE or 0)')
     args = ap.parse_args(argv)
     if not os.path.isfile(args.input_file):
@@ -56,6 +95,9 @@ def main(argv=None):
         return 1
     if args.min_size < 1:
         print(f'ERROR --min-size {args.min_size}: at least 1')
+        return 1
+    if args.max_bodies is not None and args.max_bodies < 0:
+        print(f'ERROR --max-bodies {args.max_bodies}: at least 0')
         return 1
     output = args.output or os.path.splitext(args.input_file)[0] + '_SIEVED.tif'
     engine = pipeline.engine_of(dswx_hls.get_context(args.device))
@@ -65,8 +107,16 @@ def main(argv=None):
         print(e)
         return 1
     res = plane.label(wtr_label_spec(args.min_size, connectivity=args.connectivity, partial_is_water=not args.no_partial))
-    plane.release()
     s = [int(v) for v in res['summary'].numpy()[0]]
+    rows = np.zeros(0, dtype=ROW_DTYPE)
+    if args.table is not None:
+        res['label'].shape = res['label'].shape[1:]           # [1, H, W] -> the raster of the value plane
+        table = res['label'].body_table(wtr_body_spec(s[0] if args.max_bodies is None else args.max_bodies), value=plane)
+        if 'rows' in table:
+            rows = table['rows'].numpy().view(ROW_DTYPE)[0, :, 0]
+        for p in table.values():
+            p.release()
+    plane.release()
     said = {'input_file': os.path.basename(args.input_file), 'band': args.band, 'min_size': args.min_size,
             'connectivity': args.connectivity, 'bodies': s[0], 'member_pixels': s[1], 'largest_size': s[2], 'largest_label': s[3],
             'bodies_kept': s[4], 'pixels_kept': s[5], 'bodies_by_log2_size': s[8:]}
@@ -87,6 +137,10 @@ def main(argv=None):
                          output_files_list=written, no_data_value=255)
     for p in res.values():
         p.release()
+    if args.table is not None:
+        known = geotiff.TAG_TRANSFORM in tags or (geotiff.TAG_PIXEL_SCALE in tags and geotiff.TAG_TIEPOINT in tags)
+        write_table(args.table, rows, args.min_size, info.width, tuple(float(v) for v in gt) if known else None)
+        written.append(args.table)
     for f in written:
         print(f'file saved: {f}')
     print(json.dumps(said))

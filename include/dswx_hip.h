@@ -927,6 +927,83 @@ int dswx_batch_label(dswx_batch_t* batch, int32_t plane, const dswx_label_spec_t
 int dswx_label_host(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                     int64_t tile_stride_elems, const dswx_label_out_t* out_host);
 
+/* ---- body table: the labelled bodies of a plane renumbered 1 .. K and tabulated, one 64-byte row per body (additive to ABI v7)
+ * The label entries above leave per-pixel planes and a 40-word summary; the question after labelling is per BODY: how many
+ * lakes, and for each where it is, how large, how long its shoreline, how much of it open or partial water -- or cloud on
+ * another date.  These entries answer it without the 4-byte label plane crossing PCIe, and give the dense renumbering that
+ * the label entries deliberately left out, so that per-body arrays can be indexed on the device.  The first entries here
+ * whose output size depends on the data.  A C caller tests for them with DSWX_HAS_BODY_TABLE.
+ * THE DEFINITION.  Per tile, `label` is a uint32 plane [n_tiles][height * width], dense, as dswx_label_device leaves it: 0 for
+ * a non-member, else 1 + the smallest pixel index of the body; `value` an optional uint8 plane [n_tiles][value_stride] at any
+ * address whose padding is never read.  The spec: n_cats 0 .. DSWX_BODY_MAX_CATS; cat_of_byte[256] in the convention of
+ * dswx_stack_spec_t (an entry >= n_cats: the byte is not counted); value == NULL if and only if n_cats == 0; max_rows >= 0
+ * is the capacity of the table per tile.  With idx(p) = y * width + x, a pixel with L = label[p] != 0 is WELL-FORMED iff
+ * L <= idx(p) + 1 and label[L - 1] == L.  Every other non-zero pixel is MALFORMED: it belongs to no body, gets dense 0 and is
+ * only counted in the head.  The entries never read outside the tile for ANY content of `label`: the bound on L is checked
+ * before the dependent load, so a label plane taken before its last launch, or a caller's garbage, is legal input.  The ROOTS
+ * are the pixels with label[p] == idx(p) + 1, K is their number, rank(r) the number of roots with a smaller index.
+ *   dense[p]   uint32: 0 for label 0 or a malformed pixel, else 1 + rank(label[p] - 1).  For a plane from dswx_label_* this is
+ *              exactly the array that scipy.ndimage.label returns.  REQUIRED: it is the working array of the prefix sum;
+ *   rows       [n_tiles][max_rows] rows of DSWX_BODY_ROW_WORDS uint32 (64 bytes; the 64-bit fields at even words); row k is
+ *              the body with dense == k + 1, for k < min(K, max_rows):
+ *                word 0 label; 1 area (pixels); 2, 3 x_min, x_max; 4, 5 y_min, y_max; 6-7 perimeter (uint64); 8-9 sum_x
+ *                (uint64); 10-11 sum_y (uint64); 12 .. 15 count[c]: the pixels of the body with cat_of_byte[value at p] == c
+ *                for c < n_cats, else 0.
+ *              The perimeter counts the pairs (pixel of the body, one of its four edge directions) whose neighbour is outside
+ *              the tile or holds a different label VALUE; rows do not wrap; uint64 because a checkerboard body of 2^30 pixels
+ *              has 2^32 edges.  The centroid is sum / area, left to the caller so that everything stays integer.  Rows
+ *              min(K, max_rows) .. max_rows - 1 are all zero.  Bodies of rank >= max_rows have no row, but their dense
+ *              values and their share of the head are complete: a table that is too small is truncated, never wrong (and K
+ *              is known beforehand from word 0 of the label summary);
+ *   head       uint64 [n_tiles][DSWX_BODY_HEAD_WORDS]: word 0 K; 1 min(K, max_rows); 2 well-formed member pixels; 3 malformed
+ *              pixels; 4 the sum of the perimeters of all K bodies; 5 .. 7 zero.
+ * rows and head may each be NULL = not wanted; rows NULL requires max_rows == 0.  height * width <= 2^31.  n_tiles == 0 or an
+ * empty raster writes nothing.  All of it is integer arithmetic: the result is deterministic and independent of the launch
+ * geometry and of the order in which atomics arrive. */
+#define DSWX_HAS_BODY_TABLE 1
+#define DSWX_BODY_ROW_WORDS 16
+#define DSWX_BODY_HEAD_WORDS 8
+#define DSWX_BODY_MAX_CATS 4
+typedef struct dswx_body_spec {
+    int64_t max_rows;                  /* 0 .. 2^31: rows of the table per tile */
+    int32_t n_cats;                    /* 0 .. DSWX_BODY_MAX_CATS */
+    uint8_t cat_of_byte[256];          /* category of a value byte; >= n_cats: not counted */
+} dswx_body_spec_t;                    /* 272 bytes */
+typedef struct dswx_body_out {
+    uint32_t* dense;                   /* [n_tiles][height * width]; REQUIRED: it is the working array of the prefix sum */
+    uint32_t* rows;                    /* [n_tiles][max_rows][16]; NULL = not wanted (max_rows must be 0 then) */
+    uint64_t* head;                    /* [n_tiles][8]; NULL = not wanted */
+} dswx_body_out_t;
+/* One label plane and an optional value plane [n_tiles][value_stride_elems] in DEVICE memory -> the wanted outputs of
+ * *out_device (device memory).  Asynchronous on `stream` (NULL = the context's stream): four kernel launches (count the roots
+ * of every chunk of 4096 elements into dense itself; scan those counts per tile; rank the roots and begin their rows;
+ * tabulate a rectangle per workgroup, equal bodies combined per thread, wave and workgroup before any atomic) plus one hipMemsetAsync each of `rows` and
+ * `head`; no synchronisation, no scratch of the context, no allocation, and nothing the caller has to zero in front: a second
+ * call on the same outputs gives the same bytes.  No workgroup ever waits for another: the prefix sum is reduce, scan of the
+ * partials, apply, as successive launches.  value_stride_elems 0 = height * width.  A NULL spec or out struct, n_cats outside
+ * 0 .. 4, a value plane with n_cats == 0 or none with n_cats > 0, a negative size, tile count, stride or max_rows, a stride
+ * below height * width, height * width above 2^31, a NULL dense, a NULL label with something to read, NULL rows with
+ * max_rows > 0, or max_rows above 2^31: DSWX_ERR_ARG; label or dense off 4 bytes or rows or head off 8: DSWX_ERR_ALIGN.  The
+ * value plane takes any address.  (The arguments are checked before the context is, and a refused call writes nothing; the
+ * limits on the size of a plane are those of dswx_compare_device.)  The outputs MUST NOT OVERLAP the inputs or each other:
+ * that is NOT CHECKED. */
+int dswx_body_table_device(dswx_ctx_t* ctx, const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec,
+                           int64_t n_tiles, int64_t height, int64_t width, int64_t value_stride_elems,
+                           const dswx_body_out_t* out_device, void* stream);
+/* The same for tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last) of a resident batch:
+ * `value_plane` is a uint8 DSWX_PLANE_* of the library's plane table, or -1 for none (n_cats == 0); `label_device` is the
+ * dense label plane [n_tiles][height * width] of the SAME tile range in device memory owned by the caller, for instance the
+ * `label` of dswx_batch_label; output tile 0 = tile0.  The address and the stride of the value plane are those of
+ * dswx_batch_planes.  A plane that is not uint8 (the bands, DIAG), a plane the batch does not have, or DSWX_PLANE_COUNTERS:
+ * DSWX_ERR_ARG, and dswx_last_error() names the plane.  Tile ranges: the rules of dswx_batch_compare. */
+int dswx_batch_body_table(dswx_batch_t* batch, int32_t value_plane, const dswx_body_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                          const uint32_t* label_device, const dswx_body_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++: needs no device and no context.  The other half of a comparison,
+ * not a fallback of the two entries above.  The refusals of dswx_body_table_device, except that every buffer, the uint32 and
+ * uint64 ones included, may sit at any address. */
+int dswx_body_table_host(const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
+                         int64_t height, int64_t width, int64_t value_stride_elems, const dswx_body_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -955,7 +1032,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

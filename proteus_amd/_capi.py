@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = (
     'dswx_crosstab_device', 'dswx_batch_crosstab', 'dswx_crosstab_host',
     'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host',
     'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host',
-    'dswx_label_device', 'dswx_batch_label', 'dswx_label_host')
+    'dswx_label_device', 'dswx_batch_label', 'dswx_label_host',
+    'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -58,6 +59,10 @@ GRID_MAX_CATS, GRID_MAX_CELL_PIXELS, GRID_NO_SHARE, GRID_NONE = 4, 1 << 24, 255,
 HAS_LABEL = 1                     # DSWX_HAS_LABEL: additive to ABI v7
 LABEL_SUMMARY_WORDS = 40
 LABEL_RECT_H, LABEL_RECT_W = 32, 128   # csrc/dswx_label_rule.h: the rectangle one workgroup labels in LDS (tests build shapes around its seams)
+HAS_BODY_TABLE = 1                # DSWX_HAS_BODY_TABLE: additive to ABI v7
+BODY_ROW_WORDS, BODY_HEAD_WORDS, BODY_MAX_CATS = 16, 8, 4
+BODY_CHUNK, BODY_SCAN_STEP = 4096, 256   # csrc/dswx_body_rule.h: the elements one workgroup scans, the chunk counts per step of the scan launch (tests build shapes around the seams)
+BODY_RECT_H, BODY_RECT_W = 32, 128       # csrc/dswx_body_rule.h: the rectangle whose contributions one workgroup combines in LDS
 
 
 class DswxError(RuntimeError):
@@ -222,6 +227,30 @@ class LabelOut(ctypes.Structure):
     def of(cls, label=None, size=None, sieved=None, summary=None):
         return cls(label or None, size or None, sieved or None, summary or None)
 
+
+class BodySpec(ctypes.Structure):
+    """dswx_body_spec_t; proteus_amd.bodies.Spec is the Python form."""
+    _fields_ = [('max_rows', ctypes.c_int64), ('n_cats', ctypes.c_int32), ('cat_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.max_rows, spec.n_cats)
+        ctypes.memmove(c.cat_of_byte, spec.cat_of_byte.ctypes.data, 256)
+        return c
+
+
+class BodyOut(ctypes.Structure):
+    """dswx_body_out_t: addresses, 0 / None = not wanted."""
+    _fields_ = [('dense', ctypes.c_void_p), ('rows', ctypes.c_void_p), ('head', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, dense=None, rows=None, head=None):
+        return cls(dense or None, rows or None, head or None)
+
+
+# the struct mirrors of the analytic entries by their C names (the offset tests compile the header against them)
+ANALYTIC_STRUCTS = {'dswx_label_spec_t': LabelSpec, 'dswx_label_out_t': LabelOut, 'dswx_body_spec_t': BodySpec,
+                    'dswx_body_out_t': BodyOut}
 
 COG_MAX_LEVELS = 8
 
@@ -402,6 +431,9 @@ def load_library(path=None):
         'dswx_label_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_label': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_label_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
+        'dswx_body_table_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+        'dswx_batch_body_table': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp, vp]),
+        'dswx_body_table_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -997,6 +1029,15 @@ class Context:
                                           int(height), int(width), int(tile_stride), ctypes.byref(out),
                                           ctypes.c_void_p(stream) if stream else None))
 
+    def body_table_device(self, label_ptr, value_ptr, spec, n_tiles, height, width, out, value_stride=0, stream=None):
+        """dswx_body_table_device: the bodies of one device label plane uint32 [n_tiles][height * width] renumbered and
+        tabulated against the device plane uint8 [n_tiles][value_stride] at `value_ptr` (0 / None with spec.n_cats == 0) by
+        `spec` (a bodies.Spec; include/dswx_hip.h "body table", proteus_amd/bodies.py states the definition in numpy) -> the
+        outputs `out` names (a BodyOut of device addresses); four launches and two memsets, asynchronous."""
+        _check(self.lib.dswx_body_table_device(self.handle, ctypes.c_void_p(label_ptr), ctypes.c_void_p(value_ptr) if value_ptr else None,
+                                               ctypes.byref(BodySpec.of(spec)), int(n_tiles), int(height), int(width),
+                                               int(value_stride), ctypes.byref(out), ctypes.c_void_p(stream) if stream else None))
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -1172,6 +1213,51 @@ def label_host(tiles, spec, want=('label', 'size', 'sieved', 'summary'), raster=
     out = LabelOut.of(**{k: a.ctypes.data for k, a in res.items()})
     _check(load_library().dswx_label_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(LabelSpec.of(spec)), n, H, W,
                                           stride, ctypes.byref(out)))
+    return res
+
+
+BODY_DTYPES = {'dense': np.uint32, 'rows': np.uint32, 'head': np.uint64}
+
+
+def _body_wanted(want, spec):
+    """`want` in the order of the struct; 'dense' is always made (it is the working array); 'rows' only with max_rows > 0."""
+    want = tuple(want)
+    for k in want:
+        if k not in BODY_DTYPES:
+            raise ValueError(f'unknown output {k!r} (dense, rows, head)')
+    if not want:
+        raise ValueError('no output wanted')
+    if spec.max_rows > 0 and 'rows' not in want:
+        raise ValueError(f"max_rows {spec.max_rows} without 'rows': a table that is not wanted has max_rows 0")
+    return tuple(k for k in BODY_DTYPES if k == 'dense' or (k in want and (k != 'rows' or spec.max_rows > 0)))
+
+
+def _body_shape(k, n, H, W, spec):
+    return {'dense': (n, H, W), 'rows': (n, spec.max_rows, BODY_ROW_WORDS), 'head': (n, BODY_HEAD_WORDS)}[k]
+
+
+def body_table_host(label, value, spec, want=('dense', 'rows', 'head'), raster=None):
+    """dswx_body_table_host (no device needed): the outputs of proteus_amd.bodies.body_table -- those named in `want`, and
+    'dense' always; 'rows' as uint32 [n_tiles, max_rows, 16], which `.view(bodies.ROW_DTYPE)[..., 0]` turns into records -- of
+    a host label plane uint32 [n_tiles, H, W] and a value plane uint8 [n_tiles, H, W] (None with spec.n_cats == 0), by the
+    library's scalar statement.  With raster=(H, W), `value` is a padded plane uint8 [n_tiles, value_stride], value_stride >=
+    H * W, whose padding is not read."""
+    label = np.ascontiguousarray(label)
+    if label.dtype != np.uint32 or label.ndim != 3:
+        raise ValueError(f'a label plane is uint32 [n_tiles, H, W], not {label.dtype} {label.shape}')
+    n, H, W = label.shape
+    stride = 0
+    if value is not None:
+        value = np.ascontiguousarray(value)
+        if value.dtype != np.uint8 or (value.shape != label.shape if raster is None else value.ndim != 2 or value.shape[0] != n or tuple(raster) != (H, W)):
+            raise ValueError(f'a value plane is uint8 {label.shape} or, with raster=, [n_tiles, value_stride], not {value.dtype} {value.shape}')
+        if raster is not None:
+            stride = value.shape[1]
+    res = {k: np.zeros(_body_shape(k, n, H, W, spec), dtype=BODY_DTYPES[k]) for k in _body_wanted(want, spec)}
+    out = BodyOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_body_table_host(_host_ptr(label) if label.size else None,
+                                               _host_ptr(value) if value is not None else None,
+                                               ctypes.byref(BodySpec.of(spec)), n, H, W, stride, ctypes.byref(out)))
     return res
 
 
@@ -1473,6 +1559,36 @@ class DeviceBatch:
             _check(self.ctx.lib.dswx_batch_label(self.handle, PLANE_INDEX[name], ctypes.byref(LabelSpec.of(spec)), int(tile0),
                                                  int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
                                                  ctypes.c_void_p(stream) if stream else None))
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
+
+    def body_table(self, value_name, spec, label, tile0=0, n_tiles=None, want=('dense', 'rows', 'head'), stream=None):
+        """dswx_batch_body_table: the bodies of `label` -- the device address (or a DeviceBuffer) of the dense label plane
+        uint32 [n_tiles][H*W] of tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0), for instance
+        label(...)['label'] of the same range -- renumbered and tabulated against the uint8 plane `value_name` (None with
+        spec.n_cats == 0) by `spec` (a bodies.Spec), asynchronous on `stream`.  Returns {output: DeviceBuffer} for the outputs
+        named in `want` and 'dense' always: 'dense' uint32 [n_tiles][H*W], 'rows' uint32 [n_tiles][max_rows][16] (only with
+        max_rows > 0), 'head' uint64 [n_tiles][8] -- device planes owned by the caller.  proteus_amd.bodies.body_table of
+        the downloaded planes gives the same."""
+        if value_name is not None and value_name not in PLANE_INDEX:
+            raise ValueError(f'unknown plane {value_name!r}')
+        if n_tiles == BATCH_ALL_TILES:
+            n_tiles = None
+        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        res = {}
+        for k in _body_wanted(want, spec):
+            shape = _body_shape(k, nt, self.height, self.width, spec)
+            res[k] = self.ctx.malloc(max(int(np.prod(shape, dtype=np.int64)), 1) * np.dtype(BODY_DTYPES[k]).itemsize)
+        out = BodyOut.of(**{k: b.ptr for k, b in res.items()})
+        try:
+            _check(self.ctx.lib.dswx_batch_body_table(self.handle, -1 if value_name is None else PLANE_INDEX[value_name],
+                                                      ctypes.byref(BodySpec.of(spec)), int(tile0),
+                                                      int(BATCH_ALL_TILES if n_tiles is None else n_tiles),
+                                                      ctypes.c_void_p(getattr(label, 'ptr', label)), ctypes.byref(out),
+                                                      ctypes.c_void_p(stream) if stream else None))
         except DswxError:
             for buf in res.values():
                 buf.free()

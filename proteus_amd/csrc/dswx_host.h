@@ -279,6 +279,13 @@ int dswx_label_check(const uint8_t* plane, const dswx_label_spec_t* spec, int64_
 int dswx_label_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height,
                       int64_t width, int64_t stride, const dswx_label_out_t* out, hipStream_t s);
 
+// ---- body table (dswx_body_table.hip): the shared checks of the entries (resolves a value stride of 0; `align`: label and
+// dense must be 4-byte and rows and head 8-byte aligned), and the launches for arguments that passed them
+int dswx_body_check(const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles, int64_t height,
+                    int64_t width, int64_t* stride, const dswx_body_out_t* out, bool align);
+int dswx_body_launch(dswx_ctx* ctx, const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
+                     int64_t height, int64_t width, int64_t stride, const dswx_body_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

@@ -164,6 +164,30 @@ class DevicePlane:
             self.engine.ctx.synchronize()
         return made
 
+    def body_table(self, spec, value=None, want=('dense', 'rows', 'head')):
+        """The bodies of this LABEL plane -- uint32 [n, H, W] (or one [H, W]) as label(...)['label'] leaves it in HBM --
+        renumbered 1 .. K and tabulated (dswx_body_table_device; proteus_amd.bodies.body_table of the same arrays gives the
+        same): a dict of DevicePlanes for the outputs named in `want` and 'dense' always -- 'dense' uint32 [n, H, W], 'rows'
+        uint32 [n, max_rows, 16] (only with spec.max_rows > 0; `.numpy().view(bodies.ROW_DTYPE)[..., 0]` are the records),
+        'head' uint64 [n, 8] -- which stay on the device, so plane.label(...)['label'].body_table(...) chains without a
+        download.  `value` is a uint8 DevicePlane of the same raster (None with spec.n_cats == 0); `spec` a bodies.Spec
+        (bodies.wtr_body_spec for a WTR layer as value)."""
+        if len(self.shape) not in (2, 3) or self.dtype != np.uint32:
+            raise ValueError(f'bodies are tabulated from a uint32 [n, H, W] or [H, W] label plane, not {self.dtype} {self.shape}')
+        if (value is None) != (spec.n_cats == 0):
+            raise ValueError('value is None if and only if n_cats is 0')
+        if value is not None and (value.dtype != np.uint8 or tuple(value.shape) != tuple(self.shape)):
+            raise ValueError(f'a value plane is uint8 {tuple(self.shape)}, not {value.dtype} {tuple(value.shape)}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        made = {k: self.engine.plane(_capi._body_shape(k, n_tiles, height, width, spec), _capi.BODY_DTYPES[k])
+                for k in _capi._body_wanted(want, spec)}
+        out = _capi.BodyOut.of(**{k: p.ptr for k, p in made.items()})
+        with self.engine.lock, stages.span('gpu: body table'):
+            self.engine.ctx.body_table_device(self.ptr, value.ptr if value is not None else None, spec, n_tiles, height, width, out)
+            self.engine.ctx.synchronize()
+        return made
+
     def compare(self, other, atol=0.0, rtol=0.0, equal_nan=True):
         """This raster against `other` (a DevicePlane of the same shape and dtype) as they lie in HBM (dswx_compare_device;
         proteus_amd.compare.compare_tiles of the two arrays gives the same records): compare.RECORD [n], one record per
