@@ -48,6 +48,16 @@ def bodies_of(label):
     return (flat == np.arange(1, flat.shape[1] + 1, dtype=np.uint64)).sum(axis=1)
 
 
+def malformed_tiny(H, W):
+    """uint32 [H, W] for a raster too small for `malformed` (6 pixels are enough): a root with one follower, a label above
+    the tile, a label above idx + 1 that names a later NON-member, a second root and a non-member."""
+    N = H * W
+    assert N >= 6
+    a = np.zeros(N, dtype=np.uint32)
+    a[:5] = (1, 1, N + 3, N, 5)
+    return a.reshape(H, W)
+
+
 def malformed(H, W, rng):
     """name -> uint32 [H, W]: a labelled noise raster with pixels that are malformed in one way each.  Needs bodies of more
     than one pixel and some non-members: H * W >= 64."""

@@ -94,6 +94,25 @@ def patterns(H, W, rng):
     return out
 
 
+GRID_Y = 65535                                    # the blocks of grid.y: a workgroup of the tile-loop kernels walks on to tile blockIdx.y + 65535
+EARLY = ('full', 'noise 0.9', 'checkerboard', 'serpentine')
+LATE = ('empty', 'one_pixel', 'noise 0.1', 'row_wrap')
+
+
+def second_pass_members(H, W, rng):
+    """bool [65535 + 4, H, W] for the calls in which the workgroups of tiles 0 .. 3 do a second tile with the LDS, the
+    barriers and the wave-wide state of the first: tiles 0 .. 3 are EARLY (dense), tiles 65535 .. 65538 LATE (sparse, so that
+    anything left behind shows), every other tile noise at the densities of DENSITIES in turn."""
+    T = GRID_Y + 4
+    density = np.array(DENSITIES)[np.arange(T) % len(DENSITIES)]
+    m = rng.random((T, H, W)) < density[:, None, None]
+    m[:4] = np.stack([full(H, W), noise(H, W, 0.9, rng), checkerboard(H, W), serpentine(H, W)])
+    m[GRID_Y:] = np.stack([empty(H, W), one_pixel(H, W), noise(H, W, 0.1, rng), row_wrap(H, W)])
+    for i in range(4):
+        assert not np.array_equal(m[GRID_Y + i], m[i]), (LATE[i], EARLY[i])
+    return m
+
+
 def plane_of(members, rng, only_255=False):
     """A uint8 plane of the shape of `members` and a member table: member bytes and non-member bytes are drawn from several
     values each (or, with only_255, byte 255 alone is a member), so that the table is exercised and `sieved` has bytes to

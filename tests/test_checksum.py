@@ -70,6 +70,14 @@ def test_numpy_statement_against_a_scalar_loop():
     assert checksum(a[::2, 1::3]) == scalar_checksum(a[::2, 1::3].tobytes())
     t = rng.integers(0, 256, size=(5, 9, 11), dtype=np.uint8)
     assert checksum_tiles(t).tolist() == [scalar_checksum(t[k].tobytes()) for k in range(5)]
+    # many tiles at a time: every tile length around a word and two, every element size, a view that is not contiguous
+    for nbytes in list(range(1, 26)) + [136, 4097]:
+        for dt in (np.uint8, np.int16, np.uint32, np.float64):
+            if nbytes % np.dtype(dt).itemsize == 0:
+                t = rng.integers(0, 256, size=(7, nbytes + 8), dtype=np.uint8).view(dt)[:, :nbytes // np.dtype(dt).itemsize]
+                assert checksum_tiles(t).tolist() == [scalar_checksum(t[k].tobytes()) for k in range(7)], (nbytes, dt)
+    assert checksum_tiles(np.zeros((0, 4), dtype=np.uint8)).shape == (0,)
+    assert checksum_tiles(np.zeros((3, 0), dtype=np.uint8)).tolist() == [0, 0, 0]
 
 
 def test_library_scalar_statement_against_the_numpy_statement():

@@ -3,7 +3,7 @@ statement (dswx_body_table_host, which tests/test_body_table.py pins to the nump
 either side of a 16-element load and of a row, every pattern of tests/_label_cases.py at each, both connectivities, label and
 dense at 0, 4 and 12 bytes and the value plane at 0, 1 and 3 bytes past a 16-byte boundary, padded strides, every subset of the
 outputs and capacities either side of K, with every byte outside the outputs checked; element counts around the scan chunk and
-more chunks than one step of the scan; a body per pixel and one body per tile; malformed planes; a caller's stream with the
+more chunks than one step of the scan; a body per pixel and one body per tile; malformed planes; more tiles than grid.y has blocks; a caller's stream with the
 outputs reused; the head against the label summary and the histogram; every form of batch; the DevicePlane chain;
 bin/dswx_bodies.py --table; the C example."""
 import csv
@@ -248,6 +248,44 @@ def test_malformed_planes_return_and_agree_with_the_host_entry(ctx):
     garbage = rng.integers(0, 1 << 32, size=(2, 40, 200), dtype=np.uint64).astype(np.uint32)
     garbage[1] %= 8001
     once(ctx, garbage, None, B.spec_of(0, 50), 'garbage')
+
+
+@pytest.mark.parametrize('H,W', [(2, 3), (_capi.BODY_RECT_H + 1, 2), (2, _capi.BODY_RECT_W + 1)],
+                         ids=['one_rectangle', 'two_rectangles_down', 'two_rectangles_across'])
+def test_a_workgroup_tabulates_a_second_tile_past_the_blocks_of_grid_y(ctx, H, W):
+    """65535 + 4 tiles: grid.y is 65535 (and grid.x of the scan launch), and the workgroups of tiles 0 .. 3 walk on to tiles
+    65535 .. 65538 with the `wtot` / `chunk_base` of the count and rank kernels and the `key` / `acc` / `part` of
+    dswx_body_fill_k as the first tile left them.  The label planes are dswx_label_host's (connectivity 8) of
+    tests/_label_cases.py's second-pass rasters: the first four tiles dense, the last four sparse, the rest noise; tile 65536
+    holds a MALFORMED plane instead (the host entry is the reference for it as for the rest).  A random value plane with 4
+    categories, its stride 3 above the raster and padding full of a counted byte; capacity 3, so that some tiles are
+    truncated and some are not -- at 2 x 3 no tile has more than two bodies, so that shape runs again at capacity 1.  All
+    three outputs of EVERY tile against the host entry, every byte outside the outputs checked."""
+    rng = np.random.default_rng(9996 + H + W)
+    label = B.labels_of(C.second_pass_members(H, W, rng), rng, 8)
+    T = len(label)
+    assert T == 65535 + 4
+    label[65536] = B.malformed(H, W, rng)['above_idx'] if H * W >= 64 else B.malformed_tiny(H, W)
+    for i in range(4):
+        assert not np.array_equal(label[65535 + i], label[i]), i
+    value = B.value_like(label, rng)
+    r = None
+    for max_rows in (3, 1) if H * W < 8 else (3,):
+        spec = B.spec_of(4, max_rows)
+        ref = _capi.body_table_host(label, value, spec)
+        r = Run(ctx, label, value, spec, stride=H * W + 3, loff=4, voff=1, bufs=(r.lbuf, r.vbuf, r.obuf) if r else None)
+        r.run()
+        ctx.synchronize()
+        info = ctx.last_kernel_info()
+        assert info.count(',65535,1)') == 2 and 'dswx_body_scan_k grid=(65535,1,1)' in info, info
+        r.check((H, W, max_rows), ref=ref)
+    late = ref['head'][65535:]
+    assert late[1, 3] > 0                                                  # (the malformed tile has malformed pixels)
+    truncated = late[:, 0] > late[:, 1]
+    assert truncated.any() and not truncated.all(), late[:, :2]
+    whole = ref['head'][:, 0] > ref['head'][:, 1]
+    assert 0 < np.count_nonzero(whole) < T
+    r.free()
 
 
 def test_on_a_callers_stream_twice_with_the_same_outputs(ctx):

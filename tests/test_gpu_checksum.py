@@ -1,6 +1,6 @@
 """The checksum entries of ABI v7 on the GPU: dswx_checksum_device and dswx_batch_checksum against the numpy statement of
 the definition (proteus_amd/checksum.py) on downloaded copies -- every element size, tile lengths either side of the
-kernel's 16-byte units and 4 KiB passes, tile counts, strides and plane addresses; on a caller's stream behind the
+kernel's 16-byte units and 4 KiB passes, tile counts (also past the 65535 of one launch), strides and plane addresses; on a caller's stream behind the
 kernel that writes the plane; the batch forms; and the two headline batches with EVERY tile checked against the C oracle
 through the checksums (tests/test_gpu_parity.py compares 5 of 256 and 3 of 512 tiles byte by byte)."""
 import json
@@ -13,7 +13,7 @@ import pytest
 
 from oracle import c_oracle
 from proteus_amd import _capi
-from proteus_amd.checksum import checksum
+from proteus_amd.checksum import checksum, checksum_tiles
 from proteus_amd.synth import SEED
 
 pytestmark = pytest.mark.gpu
@@ -40,14 +40,20 @@ class Plane:
     not tile data the sentinel; `tiles` are the host copies the expected values come from."""
     GUARD = 512
 
-    def __init__(self, ctx, rng, eb, n, n_tiles, stride, off, sentinel=SENT, buf=None, values=256):
+    def __init__(self, ctx, rng, eb, n, n_tiles, stride, off, sentinel=SENT, buf=None, values=256, tiles=None):
         self.ctx, self.eb, self.n, self.n_tiles, self.stride, self.off = ctx, eb, n, n_tiles, stride, off
         span = ((n_tiles - 1) * stride + n) * eb if n_tiles else 0           # the last tile's padding need not exist
         self.nbytes = self.GUARD + off + span + self.GUARD
         self.host = np.full(self.nbytes, sentinel, dtype=np.uint8)
         self.start = self.GUARD + off
-        self.tiles = []
-        for t in range(n_tiles):
+        if tiles is not None:                             # the bytes of every tile, uint8 [n_tiles, n * eb], placed in one step
+            assert tiles.shape == (n_tiles, n * eb) and tiles.dtype == np.uint8 and n_tiles > 0
+            rows = np.lib.stride_tricks.as_strided(self.host[self.start:], shape=tiles.shape, strides=(stride * eb, 1))
+            rows[...] = tiles
+            self.tiles = tiles
+        else:
+            self.tiles = []
+        for t in range(n_tiles if tiles is None else 0):
             data = rng.integers(0, values, size=n * eb, dtype=np.uint8)
             a = self.start + t * stride * eb
             self.host[a:a + n * eb] = data
@@ -142,6 +148,47 @@ def test_every_plane_address_at_full_size(ctx):
             ctx.synchronize()
             assert np.array_equal(p.result(), p.expected()), (eb, off)
         buf.free()
+
+
+SPLIT = 65535                                             # the blocks of grid.y: one launch takes this many tiles
+
+
+@pytest.mark.parametrize('eb', [1, 2, 4, 8])
+def test_more_tiles_than_one_launch_takes(ctx, eb):
+    """Tile counts either side of the 65535 tiles of one launch and past two launches (65535, 65536, 65535 + 4, 2 x 65535 + 1:
+    a third launch), tiles of 1 element (a tail only) and of 17 (one 16-byte unit and a tail with eb 1), the stride equal
+    to the tile and 3 above it, the plane one element past a 256-byte boundary.  Random bytes, so that a tile read one
+    stride off or a word written one slot off differs: EVERY checksum against the numpy statement (a few of them also
+    against the library's scalar entry), and every other byte of the buffer -- guards, padding, tiles, the words around the
+    table -- as it was."""
+    rng = np.random.default_rng(9010 + eb)
+    counts = (SPLIT, SPLIT + 1, SPLIT + 4, 2 * SPLIT + 1)
+    tail = 64                                                                  # sentinel words behind the table
+    buf = ctx.malloc(2 * Plane.GUARD + 256 + max(counts) * (17 + 3) * eb + 256 + 8 * (max(counts) + tail))
+    cases = 0
+    for n in (1, 17):
+        pool = rng.integers(0, 256, size=(max(counts), n * eb), dtype=np.uint8)
+        sums = checksum_tiles(pool)
+        for k in (0, 1, SPLIT - 1, SPLIT, SPLIT + 1, 2 * SPLIT, len(pool) - 1):
+            assert int(sums[k]) == _capi.checksum_host(pool[k]) == checksum(pool[k])
+        for n_tiles in counts:
+            for stride in (n, n + 3):
+                p = Plane(ctx, rng, eb, n, n_tiles, stride, eb, buf=buf, tiles=pool[:n_tiles])
+                words = n_tiles + tail
+                buf.upload(np.full(words, 0x1111111111111111, dtype=np.uint64), p.out_off)
+                buf.upload(np.full(p.out_off - p.nbytes + 8, SENT, dtype=np.uint8), p.nbytes - 8)
+                p.run()
+                ctx.synchronize()
+                assert f',{SPLIT},1)' in ctx.last_kernel_info(), ctx.last_kernel_info()
+                got = buf.download(np.uint64, words, p.out_off)
+                bad = np.flatnonzero(got[:n_tiles] != sums[:n_tiles])
+                assert bad.size == 0, (eb, n, n_tiles, stride, bad[:4], got[bad[:4]], sums[bad[:4]])
+                assert np.all(got[n_tiles:] == 0x1111111111111111), (eb, n, n_tiles, stride, 'words behind the table were written')
+                p.assert_untouched()
+                assert np.all(buf.download(np.uint8, p.out_off - p.nbytes + 8, p.nbytes - 8) == SENT)     # (up to the table)
+                cases += 1
+    assert cases == 2 * 4 * 2
+    buf.free()
 
 
 def test_on_a_callers_stream_behind_the_kernel_that_writes_the_plane(ctx):

@@ -1,7 +1,7 @@
 """The crosstab entries on the GPU: dswx_crosstab_device and dswx_batch_crosstab bit for bit against the numpy statement of
 the definition (proteus_amd/crosstab.py) -- every kind of plane A, tile lengths either side of the kernel's 16-pair steps, of
 an unrolled round and of a block's chunk, tile counts, the strides and the addresses of the two planes chosen independently;
-contents chosen against the accumulator and its one-value shortcut; on a caller's stream behind the kernel that replaces
+contents chosen against the accumulator and its one-value shortcut; more tiles than one launch takes; on a caller's stream behind the kernel that replaces
 plane B; every form of batch, two batches of different strides; DevicePlane.crosstab; the product comparison's tables; the
 C example."""
 import os
@@ -14,7 +14,7 @@ import pytest
 
 from oracle import dswx_oracle as o
 from proteus_amd import _capi
-from proteus_amd.crosstab import CELLS, WTR_CLASSES, WTR_VALUES, Spec, classes, crosstab, crosstab_tiles, fold
+from proteus_amd.crosstab import CELLS, WTR_CLASSES, WTR_VALUES, Spec, cell_of, classes, crosstab, crosstab_tiles, fold
 from proteus_amd.histogram import DTYPES, HIST_DIAG, HIST_I16, HIST_U16, HIST_U8, bin_of
 from proteus_amd.synth import SEED
 from tests.test_crosstab import check_printed_tables
@@ -103,6 +103,7 @@ class Pair:
             host[at:at + self.n * eb] = a_tiles[t].view(np.uint8)
             at = self.b_start + t * b_stride
             host[at:at + self.n] = b_tiles[t]
+        self.host = host
         self.out_off = -(-self.nbytes // 256) * 256
         need = self.out_off + 8 * CELLS * max(self.n_tiles, 1)
         self.buf = buf if buf is not None else ctx.malloc(need)
@@ -245,6 +246,41 @@ def test_65537_one_element_tiles_cross_the_launch_split(ctx):
     want[np.arange(T), a.astype(np.int64) * 16 + b] = 1
     assert np.array_equal(got, want)
     buf.free()
+
+
+@pytest.mark.parametrize('name', ['u8', 'u16'])
+def test_more_tiles_than_one_launch_takes_with_two_strides(ctx, name):
+    """65535 + 4 tiles of 17 pairs (one 16-pair step and a tail), plane A with a stride 3 above the tile and one element past
+    a 256-byte boundary, plane B with a stride 5 above it and 3 bytes past one: the second launch starts at tile 65535 of
+    BOTH, each by its own stride, so a swapped or shared offset shows.  Random elements and a random spec under which the
+    padding would be counted: EVERY record against the numpy statement (a few also against the library's scalar entry), and
+    every other byte of the buffer -- guards, padding, tiles, the bytes behind the records -- as it was."""
+    rng = np.random.default_rng(9850 + len(name))
+    T, n = 65535 + 4, 17
+    spec = spec_with_counted_padding(rng, name)
+    a, b = a_data(rng, name, T * n).reshape(T, n), b_data(rng, T * n).reshape(T, n)
+    cells = cell_of(a, b, spec)
+    want = np.bincount((cells + np.arange(T)[:, None] * CELLS)[cells >= 0], minlength=T * CELLS).astype(np.uint64).reshape(T, CELLS)
+    for t in (0, 1, 65534, 65535, 65536, T - 1):
+        assert np.array_equal(want[t], crosstab(a[t], b[t], spec)) and np.array_equal(want[t], _capi.crosstab_host(a[t], b[t], spec))
+    assert 0 < int(want.sum()) < T * n                        # something is counted, something excluded
+    eb = a.dtype.itemsize
+    buf = ctx.malloc(4 * Pair.GUARD + 1024 + T * (n + 3) * eb + T * (n + 5) + 8 * CELLS * T + 4096)
+    p = Pair(ctx, spec, list(a), list(b), n + 3, n + 5, eb, 3, buf=buf)
+    behind = p.out_off + 8 * CELLS * T
+    tail = np.full(p.buf.nbytes - behind, PAD, dtype=np.uint8)
+    p.buf.upload(tail, behind)
+    p.buf.upload(np.full(p.out_off - p.nbytes + 8, PAD, dtype=np.uint8), p.nbytes - 8)
+    p.run()
+    ctx.synchronize()
+    assert ',65535,1)' in ctx.last_kernel_info(), ctx.last_kernel_info()
+    got = p.result()
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, (name, bad[:4], got[tuple(bad[:4].T)], want[tuple(bad[:4].T)])
+    assert np.array_equal(p.buf.download(np.uint8, p.nbytes), p.host), 'a plane was written'
+    assert np.all(p.buf.download(np.uint8, p.out_off - p.nbytes + 8, p.nbytes - 8) == PAD)
+    assert np.all(p.buf.download(np.uint8, tail.size, behind) == PAD), 'bytes behind the records were written'
+    p.buf.free()
 
 
 def test_on_a_callers_stream_behind_the_kernel_that_replaces_plane_b(ctx):

@@ -1,7 +1,7 @@
 """The histogram entries on the GPU: dswx_histogram_device and dswx_batch_histogram bit for bit against the numpy statement
 of the definition (proteus_amd/histogram.py) -- every kind, tile lengths either side of the kernel's 16-byte units, of an
 unrolled round and of a block's chunk, tile counts, strides and plane addresses; contents chosen against the accumulator
-(constant planes, two values, every value, runs, noise); a tile of more than 2^32 elements; on a caller's stream behind
+(constant planes, two values, every value, runs, noise); a tile of more than 2^32 elements; more tiles than one launch takes, every kind; on a caller's stream behind
 the kernel that writes the plane; every form of batch; DevicePlane.histogram; the C example."""
 import os
 import shutil
@@ -13,7 +13,7 @@ import pytest
 
 from oracle import dswx_oracle as o
 from proteus_amd import _capi
-from proteus_amd.histogram import BINS, DTYPES, HIST_DIAG, HIST_I16, HIST_U16, HIST_U8, histogram, histogram_tiles
+from proteus_amd.histogram import BINS, DTYPES, HIST_DIAG, HIST_I16, HIST_U16, HIST_U8, bin_of, histogram, histogram_tiles
 from proteus_amd.synth import SEED
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +70,7 @@ class Plane:
         for t, data in enumerate(tiles):
             a = self.start + t * stride * self.eb
             host[a:a + self.n * self.eb] = data.view(np.uint8)
+        self.host = host
         self.out_off = -(-self.nbytes // 256) * 256
         need = self.out_off + 8 * BINS * max(self.n_tiles, 1)
         self.buf = buf if buf is not None else ctx.malloc(need)
@@ -239,6 +240,48 @@ def test_65537_one_element_tiles_cross_the_launch_split(ctx):
     want[np.arange(T), a] = 1
     assert np.array_equal(got, want)
     buf.free()
+
+
+@pytest.fixture(scope='module')
+def split_buffer(ctx):
+    """One buffer for the four calls of the test below (their records alone are 134 MB)."""
+    T, n = 65535 + 4, 17
+    buf = ctx.malloc(2 * Plane.GUARD + 512 + T * (n + 3) * 2 + 8 * BINS * T + 4096)
+    yield buf
+    buf.free()
+
+
+@pytest.mark.parametrize('name', list(BINNINGS))
+def test_more_tiles_than_one_launch_takes_every_kind(ctx, split_buffer, name):
+    """65535 + 4 tiles of 17 elements (one 16-byte unit and a tail for the byte kind, two units and a tail for the others),
+    the stride 3 above the tile, the plane one element past a 256-byte boundary, the linear kinds with a non-zero lo and
+    shift: the second launch starts at tile 65535.  Random elements, so that a tile read one stride off or a record written
+    one slot off differs: EVERY record against the numpy statement (a few also against the library's scalar entry), and every
+    other byte of the buffer -- guards, padding, tiles, the bytes behind the records -- as it was."""
+    rng = np.random.default_rng(7350 + len(name))
+    T, n = 65535 + 4, 17
+    kind, lo, shift = BINNINGS[name]
+    assert name in ('u8', 'diag') or (lo != 0 and shift != 0)
+    tiles = tile_data(rng, name, T * n).reshape(T, n)
+    bins = bin_of(tiles, kind, lo, shift)
+    flat = (bins + np.arange(T)[:, None] * BINS)[bins >= 0]
+    want = np.bincount(flat, minlength=T * BINS).astype(np.uint64).reshape(T, BINS)
+    for t in (0, 1, 65534, 65535, 65536, T - 1):
+        assert np.array_equal(want[t], histogram(tiles[t], kind, lo, shift)) and np.array_equal(want[t], _capi.histogram_host(tiles[t], kind, lo, shift))
+    eb = tiles.dtype.itemsize
+    p = Plane(ctx, name, list(tiles), n + 3, eb, buf=split_buffer)
+    behind = p.out_off + 8 * BINS * T
+    split_buffer.upload(np.full(split_buffer.nbytes - behind, PAD, dtype=np.uint8), behind)
+    split_buffer.upload(np.full(p.out_off - p.nbytes + 8, PAD, dtype=np.uint8), p.nbytes - 8)
+    p.run()
+    ctx.synchronize()
+    assert ',65535,1)' in ctx.last_kernel_info(), ctx.last_kernel_info()
+    got = p.result()
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, (name, bad[:4], got[tuple(bad[:4].T)], want[tuple(bad[:4].T)])
+    assert np.array_equal(split_buffer.download(np.uint8, p.nbytes), p.host), 'the plane was written'
+    assert np.all(split_buffer.download(np.uint8, p.out_off - p.nbytes + 8, p.nbytes - 8) == PAD)
+    assert np.all(split_buffer.download(np.uint8, split_buffer.nbytes - behind, behind) == PAD), 'bytes behind the records were written'
 
 
 def test_on_a_callers_stream_behind_the_kernel_that_writes_the_plane(ctx):

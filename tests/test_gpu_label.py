@@ -2,7 +2,7 @@
 (dswx_label_host, which tests/test_label.py pins to the numpy statement and to scipy) on all four outputs -- heights and widths
 either side of the rectangle one workgroup labels in LDS and of a 16-byte load, every pattern of tests/_label_cases.py at
 each, both connectivities, the plane at odd addresses, padded strides, every legal subset of the outputs, with every byte
-outside the output planes checked; the deepest chains across seams; a caller's stream with the outputs reused; every form of
+outside the output planes checked; the deepest chains across seams; more tiles than grid.y has blocks; a caller's stream with the outputs reused; every form of
 batch; the results as device planes; the summary against counts made another way; bin/dswx_bodies.py; the C example."""
 import ctypes
 import importlib.util
@@ -245,6 +245,39 @@ def test_the_result_of_tile_0_does_not_depend_on_the_number_of_tiles(ctx):
     assert len(seen) == 1
     ref = _capi.label_host(tiles[:1], spec)
     assert seen == {tuple(checksum(ref[k].view(np.uint8).reshape(-1)) for k in KEYS)}
+
+
+@pytest.mark.parametrize('H,W', [(2, 3), (R + 1, 2), (2, CW + 1)], ids=['one_rectangle', 'horizontal_seam', 'vertical_seam'])
+def test_a_workgroup_labels_a_second_tile_past_the_blocks_of_grid_y(ctx, H, W):
+    """65535 + 4 tiles: grid.y is 65535, and the workgroups of tiles 0 .. 3 walk on to tiles 65535 .. 65538 with the `lab` /
+    `msk` of dswx_label_local_k and the `part` of dswx_label_finish_k as the first tile left them.  The first four tiles are
+    dense (full, noise 0.9, checkerboard, serpentine), the last four sparse (empty, one pixel, noise 0.1, row wrap), the rest
+    noise.  2 x 3: one rectangle, loaded byte by byte, no seam launch; (R + 1) x 2: a horizontal seam; 2 x (CW + 1): a
+    vertical seam and a ragged last 16-byte segment.  Both connectivities, all four outputs of EVERY tile against the host
+    entry, min_size 2 (sieved changes bytes), the stride 5 above the raster, the plane one byte past a 256-byte boundary,
+    padding and guards full of a member byte; every byte outside the outputs checked."""
+    rng = np.random.default_rng(9550 + H + W)
+    members = C.second_pass_members(H, W, rng)
+    T = len(members)
+    assert T == 65535 + 4
+    for i in range(4):
+        assert not np.array_equal(members[65535 + i], members[i]), (C.LATE[i], C.EARLY[i])
+    tiles, table = C.plane_of(members, rng)
+    r = None
+    for conn in (4, 8):
+        spec = Spec(conn, 2, table, replace=77)
+        ref = _capi.label_host(tiles, spec)
+        assert np.count_nonzero(ref['sieved'] != tiles) > T // 8           # (single pixels are common in the noise)
+        assert not ref['summary'][65535].any() and ref['summary'][0, 0] == 1 and ref['summary'][0, 2] == H * W
+        r = Run(ctx, tiles, spec, stride=H * W + 5, off=1, sbuf=r.sbuf if r else None, obuf=r.obuf if r else None)
+        r.run()
+        ctx.synchronize()
+        info = ctx.last_kernel_info()
+        assert info.count(',65535,1)') == 2 and f'connectivity={conn}' in info, info
+        assert ('pixels=0 ' in info) == ((H, W) == (2, 3)), info
+        r.check((H, W, conn), ref=ref)
+    r.sbuf.free()
+    r.obuf.free()
 
 
 def test_summary_words_0_and_1_counted_another_way(ctx):
