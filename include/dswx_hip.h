@@ -1004,6 +1004,81 @@ int dswx_batch_body_table(dswx_batch_t* batch, int32_t value_plane, const dswx_b
 int dswx_body_table_host(const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
                          int64_t height, int64_t width, int64_t value_stride_elems, const dswx_body_out_t* out_host);
 
+/* ---- distance: the exact Euclidean distance of every pixel to the nearest target of a plane (additive to ABI v7)
+ * The entries above say what a plane holds, per pixel, per cell and per body.  These say HOW FAR: for every pixel the squared
+ * distance to the nearest water (or cloud, or any set of bytes), which target that is, the ring of pixels within a radius of
+ * a shoreline, and a per-tile summary -- without the plane crossing PCIe; the results are planes in device memory that
+ * dswx_histogram_device and dswx_checksum_device accept, and `nearest` looked up in a `label` plane of dswx_label_device says
+ * which body a pixel is nearest to.  A C caller tests for the entries with DSWX_HAS_DISTANCE.
+ * THE DEFINITION.  A plane is uint8 [n_tiles][tile_stride] at any address.  The first height * width bytes of a tile are its
+ * raster, rows contiguous with a row pitch of `width`; the padding up to the stride is never read.  Rows do not wrap and tiles
+ * never see each other.  Pixel q is a TARGET iff target_of_byte[byte at q] != 0.  With idx(p) = y * width + x,
+ * d2(p, q) = (yp - yq)^2 + (xp - xq)^2 and R = max_radius (0 = unbounded), a target q REACHES p when R == 0 or
+ * d2(p, q) <= R * R.  Per tile:
+ *   dist2[p]    uint32: the minimum of d2(p, q) over the targets that reach p; 0 on a target; DSWX_DISTANCE_NONE when no
+ *               target reaches p, which includes a tile without targets.  For R == 0 and a tile with a target this is the
+ *               square of scipy.ndimage.distance_transform_edt of the non-targets, exactly.  REQUIRED: it is the working
+ *               array between the launches;
+ *   nearest[p]  uint32: idx(q) of the target that attains it; ties go to the smallest column, then the smallest row, that is,
+ *               lexicographic in (d2, xq, yq) -- the tie a separable transform produces naturally: the column pass ties
+ *               upward, the row pass ties leftward.  DSWX_DISTANCE_NONE where dist2 is;
+ *   within[p]   uint8: the input byte, except that a non-target p with dist2[p] != DSWX_DISTANCE_NONE becomes `mark`: the
+ *               buffer ring.  Only meaningful with R > 0: wanted with R == 0 is refused;
+ *   summary     uint64 [DSWX_DISTANCE_SUMMARY_WORDS] per tile: word 0 targets; 1 reached non-target pixels; 2 pixels not
+ *               reached; 3 the largest dist2 among reached pixels (0 when none); 4 idx of the pixel holding it (the smallest
+ *               idx on a tie, 0 when none); 5 the sum of dist2 over reached pixels; 6, 7 zero; 8 + b, b = 0 .. 31, the reached
+ *               non-target pixels with floor(log2(dist2)) == b.
+ * height and width are each at most 46340, so that (height - 1)^2 + (width - 1)^2 stays below DSWX_DISTANCE_NONE;
+ * height * width <= 2^31; width <= DSWX_DISTANCE_MAX_WIDTH: the row pass keeps one whole row of the working array in LDS,
+ * 4 bytes a pixel plus three words per 64 columns, which at 8192 columns is 34 KiB a workgroup -- four workgroups (sixteen
+ * waves) stay resident in the 160 KiB of a compute unit.  n_tiles == 0 or an empty raster writes nothing.  All of it is
+ * integer arithmetic: the result is deterministic and independent of the launch geometry and of the order in which atomics
+ * arrive. */
+#define DSWX_HAS_DISTANCE 1
+#define DSWX_DISTANCE_NONE 0xFFFFFFFFu
+#define DSWX_DISTANCE_SUMMARY_WORDS 40
+#define DSWX_DISTANCE_MAX_WIDTH 8192
+#define DSWX_DISTANCE_MAX_SIDE 46340
+typedef struct dswx_distance_spec {
+    uint32_t max_radius;               /* R in pixels; 0 = unbounded */
+    int32_t mark;                      /* 0 .. 255: the byte of a reached non-target in `within` */
+    uint8_t target_of_byte[256];       /* != 0: a pixel with this byte is a target */
+} dswx_distance_spec_t;                /* 264 bytes */
+typedef struct dswx_distance_out {     /* planes [n_tiles][height * width], dense; summary [n_tiles][40] */
+    uint32_t* dist2;                   /* REQUIRED: it is the working array between the column pass and the row pass */
+    uint32_t* nearest;                 /* NULL = not wanted */
+    uint8_t*  within;                  /* NULL = not wanted; requires max_radius > 0 */
+    uint64_t* summary;                 /* NULL = not wanted */
+} dswx_distance_out_t;
+/* One plane [n_tiles][tile_stride_elems] in DEVICE memory -> the wanted planes of *out_device (device memory).  Asynchronous
+ * on `stream` (NULL = the context's stream): at most four kernel launches (note the targets of every band of 64 rows; the
+ * vertical offset to the nearest target of the column for every pixel, with the carry across bands read from those notes; the
+ * row pass, which finishes dist2 in place and writes nearest, within and the summary; unpack the summary's largest-distance
+ * key) plus one hipMemsetAsync of `summary`; no synchronisation, no scratch of the context, no allocation, and nothing the
+ * caller has to zero in front: a second call on the same outputs gives the same result.  No workgroup ever waits for another.
+ * tile_stride_elems 0 = height * width.  A NULL spec or out struct, `mark` outside 0 .. 255, a negative size, tile count or
+ * stride, a stride below height * width, height or width above 46340, height * width above 2^31, width above
+ * DSWX_DISTANCE_MAX_WIDTH, a NULL plane with something to read, a NULL dist2, or `within` wanted with max_radius == 0:
+ * DSWX_ERR_ARG; dist2 or nearest off 4 bytes or summary off 8: DSWX_ERR_ALIGN.  The plane and `within` take any address.
+ * (The arguments are checked before the context is, and a refused call writes nothing; the limits on the size of a plane are
+ * those of dswx_compare_device.)  The outputs MUST NOT OVERLAP the plane or each other: that is NOT CHECKED. */
+int dswx_distance_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height,
+                         int64_t width, int64_t tile_stride_elems, const dswx_distance_out_t* out_device, void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table: Fmask, the masks, every layer but DIAG) of a resident
+ * batch, tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last) -> the wanted planes of
+ * *out_device: device planes owned by the caller, output tile 0 = tile0.  Asynchronous on `stream` (NULL = the stream of the
+ * batch's context) like dswx_distance_device.  The address and the stride are those of dswx_batch_planes, so packed,
+ * separate-output, placed, padded and contiguous batches are alike.  A plane that is not uint8 (the bands, DIAG), a plane the
+ * batch does not have, or DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the plane.  Tile ranges: the rules
+ * of dswx_batch_compare. */
+int dswx_batch_distance(dswx_batch_t* batch, int32_t plane, const dswx_distance_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                        const dswx_distance_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++: needs no device and no context.  The other half of a comparison,
+ * not a fallback of the two entries above.  The refusals of dswx_distance_device, except that every buffer, the uint32 and
+ * uint64 ones included, may sit at any address. */
+int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                       int64_t tile_stride_elems, const dswx_distance_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1032,7 +1107,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -44,7 +44,8 @@ EXPORTED_SYMBOLS = (
     'dswx_stack_device', 'dswx_batch_stack', 'dswx_stack_host',
     'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host',
     'dswx_label_device', 'dswx_batch_label', 'dswx_label_host',
-    'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host')
+    'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host',
+    'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -63,6 +64,11 @@ HAS_BODY_TABLE = 1                # DSWX_HAS_BODY_TABLE: additive to ABI v7
 BODY_ROW_WORDS, BODY_HEAD_WORDS, BODY_MAX_CATS = 16, 8, 4
 BODY_CHUNK, BODY_SCAN_STEP = 4096, 256   # csrc/dswx_body_rule.h: the elements one workgroup scans, the chunk counts per step of the scan launch (tests build shapes around the seams)
 BODY_RECT_H, BODY_RECT_W = 32, 128       # csrc/dswx_body_rule.h: the rectangle whose contributions one workgroup combines in LDS
+HAS_DISTANCE = 1                  # DSWX_HAS_DISTANCE: additive to ABI v7
+DISTANCE_NONE, DISTANCE_SUMMARY_WORDS, DISTANCE_MAX_WIDTH, DISTANCE_MAX_SIDE = 0xFFFFFFFF, 40, 8192, 46340
+# csrc/dswx_distance_rule.h: the rows and the columns of a column-pass thread, the columns of a block of the row pass and how far
+# the row pass looks to either side before it turns to the blocks (tests build shapes around the seams)
+DISTANCE_BAND_H, DISTANCE_COLS, DISTANCE_BLOCK_W, DISTANCE_NEAR = 64, 4, 64, 32
 
 
 class DswxError(RuntimeError):
@@ -248,9 +254,29 @@ class BodyOut(ctypes.Structure):
         return cls(dense or None, rows or None, head or None)
 
 
+class DistanceSpec(ctypes.Structure):
+    """dswx_distance_spec_t; proteus_amd.distance.Spec is the Python form."""
+    _fields_ = [('max_radius', ctypes.c_uint32), ('mark', ctypes.c_int32), ('target_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.max_radius, spec.mark)
+        ctypes.memmove(c.target_of_byte, spec.target_of_byte.ctypes.data, 256)
+        return c
+
+
+class DistanceOut(ctypes.Structure):
+    """dswx_distance_out_t: plane addresses, 0 / None = not wanted."""
+    _fields_ = [('dist2', ctypes.c_void_p), ('nearest', ctypes.c_void_p), ('within', ctypes.c_void_p), ('summary', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, dist2=None, nearest=None, within=None, summary=None):
+        return cls(dist2 or None, nearest or None, within or None, summary or None)
+
+
 # the struct mirrors of the analytic entries by their C names (the offset tests compile the header against them)
 ANALYTIC_STRUCTS = {'dswx_label_spec_t': LabelSpec, 'dswx_label_out_t': LabelOut, 'dswx_body_spec_t': BodySpec,
-                    'dswx_body_out_t': BodyOut}
+                    'dswx_body_out_t': BodyOut, 'dswx_distance_spec_t': DistanceSpec, 'dswx_distance_out_t': DistanceOut}
 
 COG_MAX_LEVELS = 8
 
@@ -431,6 +457,9 @@ def load_library(path=None):
         'dswx_label_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_label': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_label_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
+        'dswx_distance_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
+        'dswx_batch_distance': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
+        'dswx_distance_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
         'dswx_body_table_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_body_table': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp, vp]),
         'dswx_body_table_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp]),
@@ -1029,6 +1058,15 @@ class Context:
                                           int(height), int(width), int(tile_stride), ctypes.byref(out),
                                           ctypes.c_void_p(stream) if stream else None))
 
+    def distance_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
+        """dswx_distance_device: the squared distance of every pixel of one device plane uint8 [n_tiles][tile_stride], every
+        tile a height x width raster, to the nearest target by `spec` (a distance.Spec; include/dswx_hip.h "distance",
+        proteus_amd/distance.py states the definition in numpy) -> the planes `out` names (a DistanceOut of device addresses);
+        a fixed number of launches, asynchronous."""
+        _check(self.lib.dswx_distance_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(DistanceSpec.of(spec)), int(n_tiles),
+                                             int(height), int(width), int(tile_stride), ctypes.byref(out),
+                                             ctypes.c_void_p(stream) if stream else None))
+
     def body_table_device(self, label_ptr, value_ptr, spec, n_tiles, height, width, out, value_stride=0, stream=None):
         """dswx_body_table_device: the bodies of one device label plane uint32 [n_tiles][height * width] renumbered and
         tabulated against the device plane uint8 [n_tiles][value_stride] at `value_ptr` (0 / None with spec.n_cats == 0) by
@@ -1213,6 +1251,50 @@ def label_host(tiles, spec, want=('label', 'size', 'sieved', 'summary'), raster=
     out = LabelOut.of(**{k: a.ctypes.data for k, a in res.items()})
     _check(load_library().dswx_label_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(LabelSpec.of(spec)), n, H, W,
                                           stride, ctypes.byref(out)))
+    return res
+
+
+DISTANCE_DTYPES = {'dist2': np.uint32, 'nearest': np.uint32, 'within': np.uint8, 'summary': np.uint64}
+
+
+def _distance_wanted(want, spec):
+    """`want` in the order of the struct; 'dist2' is always made (it is the working array); 'within' needs a radius."""
+    want = tuple(want)
+    for k in want:
+        if k not in DISTANCE_DTYPES:
+            raise ValueError(f'unknown output {k!r} (dist2, nearest, within, summary)')
+    if not want:
+        raise ValueError('no output wanted')
+    if 'within' in want and spec.max_radius == 0:
+        raise ValueError("'within' is wanted but max_radius is 0: the ring needs a radius")
+    return tuple(k for k in DISTANCE_DTYPES if k == 'dist2' or k in want)
+
+
+def _distance_refuse(H, W):
+    """The limits of include/dswx_hip.h "distance" on a raster, refused here as the library would."""
+    if H > DISTANCE_MAX_SIDE or W > DISTANCE_MAX_SIDE or H * W > 1 << 31:
+        raise ValueError(f'{H} x {W} pixels: each side at most {DISTANCE_MAX_SIDE} and at most 2^31 pixels')
+    if W > DISTANCE_MAX_WIDTH:
+        raise ValueError(f'width {W} above DISTANCE_MAX_WIDTH ({DISTANCE_MAX_WIDTH})')
+
+
+def distance_host(tiles, spec, want=('dist2', 'nearest', 'summary'), raster=None):
+    """dswx_distance_host (no device needed): the planes of proteus_amd.distance.distance_tiles -- those named in `want`, and
+    'dist2' always -- of a host plane uint8 [n_tiles, H, W], by the library's scalar transform.  With raster=(H, W), `tiles`
+    is a padded plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
+    if raster is None:
+        (n, H, W), stride = tiles.shape, 0
+    else:
+        (n, stride), (H, W) = tiles.shape, raster
+    _distance_refuse(H, W)
+    res = {k: np.zeros((n, DISTANCE_SUMMARY_WORDS) if k == 'summary' else (n, H, W), dtype=DISTANCE_DTYPES[k])
+           for k in _distance_wanted(want, spec)}
+    out = DistanceOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_distance_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(DistanceSpec.of(spec)), n, H, W,
+                                             stride, ctypes.byref(out)))
     return res
 
 
@@ -1559,6 +1641,31 @@ class DeviceBatch:
             _check(self.ctx.lib.dswx_batch_label(self.handle, PLANE_INDEX[name], ctypes.byref(LabelSpec.of(spec)), int(tile0),
                                                  int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
                                                  ctypes.c_void_p(stream) if stream else None))
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
+
+    def distance(self, name, spec, tile0=0, n_tiles=None, want=('dist2', 'nearest', 'summary'), stream=None):
+        """dswx_batch_distance: the squared distance to the nearest target, by `spec` (a distance.Spec), of every pixel of tiles
+        tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of the uint8 plane `name`, asynchronous on `stream`.
+        Returns {output: DeviceBuffer} for the outputs named in `want` and 'dist2' always: 'dist2' and 'nearest' uint32
+        [n_tiles][H*W], 'within' uint8 [n_tiles][H*W] (needs spec.max_radius > 0), 'summary' uint64 [n_tiles][40] -- device
+        planes owned by the caller.  proteus_amd.distance.distance_tiles of the downloaded tiles gives the same planes."""
+        if name not in PLANE_INDEX:
+            raise ValueError(f'unknown plane {name!r}')
+        if n_tiles == BATCH_ALL_TILES:
+            n_tiles = None
+        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        px = self.height * self.width
+        res = {k: self.ctx.malloc(max(nt * (DISTANCE_SUMMARY_WORDS if k == 'summary' else px), 1) * np.dtype(DISTANCE_DTYPES[k]).itemsize)
+               for k in _distance_wanted(want, spec)}
+        out = DistanceOut.of(**{k: b.ptr for k, b in res.items()})
+        try:
+            _check(self.ctx.lib.dswx_batch_distance(self.handle, PLANE_INDEX[name], ctypes.byref(DistanceSpec.of(spec)), int(tile0),
+                                                    int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
+                                                    ctypes.c_void_p(stream) if stream else None))
         except DswxError:
             for buf in res.values():
                 buf.free()

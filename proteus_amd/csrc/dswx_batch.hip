@@ -576,6 +576,29 @@ int dswx_batch_body_table(dswx_batch_t* b, int32_t plane, const dswx_body_spec_t
     return dswx_body_launch(ctx, label, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
 }
 
+// The distance of every pixel to the nearest target in ONE uint8 plane of a resident batch (dswx_distance.hip), asynchronous:
+// the outputs are the caller's device planes, so nothing is allocated, copied or waited for here.
+int dswx_batch_distance(dswx_batch_t* b, int32_t plane, const dswx_distance_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                        const dswx_distance_out_t* out, void* stream) {
+    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
+    if (plane == DSWX_PLANE_COUNTERS)
+        return dswx_fail(DSWX_ERR_ARG, "the counters have no distances (three int64 per tile): read them (dswx_batch_planes)");
+    const dswx_plane_desc& d = DSWX_PLANES[plane];
+    if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "distances are measured in a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
+    if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
+    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
+    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
+        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
+                         (long long)n_tiles, (long long)b->geom.n_tiles);
+    int64_t stride = b->geom.tile_stride;
+    const uint8_t* base = (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride;
+    if (int rc = dswx_distance_check(base, spec, n_tiles, b->geom.height, b->geom.width, &stride, out, true)) return rc;
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return dswx_distance_launch(ctx, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

@@ -286,6 +286,13 @@ int dswx_body_check(const uint32_t* label, const uint8_t* value, const dswx_body
 int dswx_body_launch(dswx_ctx* ctx, const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
                      int64_t height, int64_t width, int64_t stride, const dswx_body_out_t* out, hipStream_t s);
 
+// ---- distance (dswx_distance.hip): the shared checks of the entries (resolves a stride of 0; `align`: dist2 and nearest
+// must be 4-byte and summary 8-byte aligned), and the launches for arguments that passed them
+int dswx_distance_check(const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                        int64_t* stride, const dswx_distance_out_t* out, bool align);
+int dswx_distance_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height,
+                         int64_t width, int64_t stride, const dswx_distance_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

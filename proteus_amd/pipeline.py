@@ -164,6 +164,26 @@ class DevicePlane:
             self.engine.ctx.synchronize()
         return made
 
+    def distance(self, spec, want=('dist2', 'nearest', 'summary')):
+        """The squared distance of every pixel of a [n, H, W] (or one [H, W]) uint8 plane to the nearest target, as the plane
+        lies in HBM (dswx_distance_device; proteus_amd.distance.distance_tiles of the same array gives the same planes): a
+        dict of DevicePlanes for the outputs named in `want` and 'dist2' always -- 'dist2' and 'nearest' uint32 [n, H, W],
+        'within' uint8 [n, H, W] (needs spec.max_radius > 0), 'summary' uint64 [n, 40] -- which stay on the device: 'within'
+        can be histogrammed, gridded or written, every one checksummed.  `spec` is a distance.Spec
+        (distance.wtr_distance_spec for a WTR layer)."""
+        if len(self.shape) not in (2, 3) or self.dtype != np.uint8:
+            raise ValueError(f'distances are measured in a uint8 [n, H, W] or [H, W] plane, not {self.dtype} {self.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        _capi._distance_refuse(height, width)
+        made = {k: self.engine.plane((n_tiles, _capi.DISTANCE_SUMMARY_WORDS) if k == 'summary' else (n_tiles, height, width),
+                                     _capi.DISTANCE_DTYPES[k]) for k in _capi._distance_wanted(want, spec)}
+        out = _capi.DistanceOut.of(**{k: p.ptr for k, p in made.items()})
+        with self.engine.lock, stages.span('gpu: distance'):
+            self.engine.ctx.distance_device(self.ptr, spec, n_tiles, height, width, out)
+            self.engine.ctx.synchronize()
+        return made
+
     def body_table(self, spec, value=None, want=('dense', 'rows', 'head')):
         """The bodies of this LABEL plane -- uint32 [n, H, W] (or one [H, W]) as label(...)['label'] leaves it in HBM --
         renumbered 1 .. K and tabulated (dswx_body_table_device; proteus_amd.bodies.body_table of the same arrays gives the
