@@ -1079,6 +1079,95 @@ int dswx_batch_distance(dswx_batch_t* batch, int32_t plane, const dswx_distance_
 int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                        int64_t tile_stride_elems, const dswx_distance_out_t* out_host);
 
+/* ---- outline: the regions of an id plane traced as ordered rings of pixel edges (additive to ABI v7)
+ * The body table above says how long a shoreline is; users of a water-extent product then ask for the lake POLYGONS.  These
+ * entries put the edges that the body table's perimeter counts in order, ring after ring, without the 4-byte label plane
+ * crossing PCIe: what comes back is 4 bytes per edge and 32 bytes per ring.  A C caller tests for them with DSWX_HAS_OUTLINE.
+ * THE DEFINITION.  `ids` is a uint32 plane [n_tiles][height * width], dense, typically the `label` of dswx_label_device or
+ * the `dense` of dswx_body_table_device: 0 is background, any other value the id of the region the pixel belongs to.  ANY
+ * CONTENT IS LEGAL: ids are only compared for equality and never used as an index.  idx(p) = y * width + x; rows do not wrap,
+ * tiles never see each other, outside the tile counts as 0.
+ *   EDGES      a boundary edge is a pair (pixel p with ids[p] = v != 0, direction d) whose neighbour across d is outside the
+ *              tile or holds a different value: exactly the pair that the body table's perimeter counts.  Its KEY is
+ *              4 * idx(p) + d, a uint32, hence height * width <= 2^30.  On pixel corners, x right and y down: d = 0 the top
+ *              edge from (x, y) to (x+1, y); 1 the right edge from (x+1, y) to (x+1, y+1); 2 the bottom edge from (x+1, y+1)
+ *              to (x, y+1); 3 the left edge from (x, y+1) to (x, y).  The region lies on the right of the direction of
+ *              travel: outer rings run clockwise on screen, holes the other way.
+ *   SUCCESSOR  with T[d] = (1,0), (0,1), (-1,0), (0,-1) the travel of edge d and O[d] = (0,-1), (1,0), (0,1), (-1,0) the step
+ *              across it: A = p + T[d] is the pixel ahead on the region's side, B = A + O[d] the one ahead on the other side,
+ *              a = (ids[A] == v), b = (ids[B] == v), both false outside the tile.  connectivity 4: if !a the successor is
+ *              4 * idx(p) + (d+1)%4 (turn right), else if !b 4 * idx(A) + d (straight), else 4 * idx(B) + (d+3)%4 (turn left).
+ *              connectivity 8: if b 4 * idx(B) + (d+3)%4, else if a 4 * idx(A) + d, else 4 * idx(p) + (d+1)%4.  The two differ
+ *              only where two pixels of one id touch at a corner.  The successor is always a boundary edge and the map a
+ *              bijection, so the edges fall into cycles: the RINGS.  A ring STARTS at its smallest key; the rings of a tile
+ *              are ORDERED by their start keys; E is the number of edges of the tile and R the number of its rings.  Every
+ *              body of a dswx_label_* plane outlined with the connectivity it was labelled with has exactly one ring of
+ *              positive area, whose start key is 4 * (label - 1); its holes are the enclosed components of its complement.
+ *   chain      uint32 [n_tiles][max_edges]: the keys of all E edges, ring after ring in ring order, each ring from its start
+ *              along the successor map; entries E .. max_edges - 1 are zero;
+ *   rings      [n_tiles][max_rings] rows of DSWX_OUTLINE_ROW_WORDS uint32 (32 bytes; the 64-bit field at an even word): word 0
+ *              the id v; 1 the start key; 2 the offset of the ring in `chain`; 3 its length in edges; 4 its corners: the edges
+ *              whose direction differs from their predecessor's, which are the vertices of the polygon once collinear points
+ *              are dropped (a single pixel has 4); 5 zero; 6-7 area2 (int64): the sum over the ring's edges of
+ *              x1 * y2 - x2 * y1, start corner 1 and end corner 2, twice the signed area, positive for an outer ring and
+ *              negative for a hole.  Rows min(R, max_rings) .. max_rings - 1 are zero.  The chain of a tile is complete even
+ *              when R > max_rings: a ring table that is too small is truncated, never wrong;
+ *   head       uint64 [n_tiles][DSWX_OUTLINE_HEAD_WORDS]: word 0 E; 1 R; 2 min(R, max_rings); 3 the edges written, which is E
+ *              when the tile fits; 4 the rings with area2 > 0; 5 those with area2 < 0; 6 the sum of the corners; 7 1 when
+ *              E > max_edges.  When E > max_edges, words 1 .. 6 are 0 and the tile's chain and rings are all zero: the caller
+ *              learns E and calls again.
+ * chain, rings and head may each be NULL = not wanted; rings NULL requires max_rings == 0, chain NULL requires rings NULL; a
+ * call with only head is the counting call.  All of it is integer arithmetic: the result is deterministic and independent of
+ * the launch geometry and of the order in which atomics arrive.
+ * NO dswx_batch_* FORM: the input is a label plane owned by the caller, not a plane of the batch; the `label` that
+ * dswx_batch_label left is passed to dswx_outline_device as it is. */
+#define DSWX_HAS_OUTLINE 1
+#define DSWX_OUTLINE_ROW_WORDS 8
+#define DSWX_OUTLINE_HEAD_WORDS 8
+typedef struct dswx_outline_spec {
+    int64_t max_edges;                 /* 0 .. 2^31: entries of `chain` per tile */
+    int64_t max_rings;                 /* 0 .. 2^31: rows of `rings` per tile */
+    int32_t connectivity;              /* 4 or 8 */
+    int32_t reserved;                  /* zero */
+} dswx_outline_spec_t;                 /* 24 bytes */
+typedef struct dswx_outline_out {
+    uint32_t* chain;                   /* [n_tiles][max_edges]; NULL = not wanted (rings must be NULL then) */
+    uint32_t* rings;                   /* [n_tiles][max_rings][8]; NULL = not wanted (max_rings must be 0 then) */
+    uint64_t* head;                    /* [n_tiles][8]; NULL = not wanted */
+} dswx_outline_out_t;
+/* The bytes of working memory that dswx_outline_device needs for these arguments, at least 16.  THE FIRST ENTRY THAT NEEDS
+ * WORKING MEMORY OF THE CALLER: the earlier entries work inside their own outputs, but here the working set is 36 bytes per
+ * edge of capacity and 5 per pixel (two copies of a 16-byte state per edge, between which the rounds alternate, 16 bytes per
+ * four edges for the sums of a ring, the number of the first edge and the edge mask of every pixel), several times all the
+ * outputs together, sized by a capacity only the caller knows, and the entry may neither allocate nor touch the context's
+ * scratch.  The capacity that counts is min(max_edges, 4 * height * width).  A NULL spec or `bytes`, a negative size, a
+ * raster above 2^30 pixels or max_edges above 2^31: DSWX_ERR_ARG. */
+int dswx_outline_work_bytes(const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width, uint64_t* bytes);
+/* One id plane in DEVICE memory -> the wanted outputs of *out_device (device memory), with `work_device` (device memory of
+ * at least dswx_outline_work_bytes bytes, whose content before and after the call means nothing) as the working memory.
+ * Asynchronous on `stream` (NULL = the context's stream): 9 + N kernel launches, N = ceil(log2(min(max_edges, 4 * height *
+ * width))) <= 31 -- count the edges of every chunk of 4096 pixels; scan those counts per tile; number the first edge of every
+ * pixel; emit for every edge its key and the number of its successor; N rounds of pointer jumping, one launch each, after
+ * which every edge knows the start of its ring and its distance to it (the number of rounds is fixed by the capacity, so that
+ * nothing is read back; the workgroups of a tile return at once when a flag in the working memory says that the round before
+ * changed nothing for that tile); count, scan and rank the ring starts, carrying count and length together; scatter the keys
+ * into the chain, the sums of a ring combined per wave before any atomic; finish the rows and the head -- plus one
+ * hipMemsetAsync each of `chain` and `rings`; no synchronisation, no scratch of the context, no allocation, and nothing the
+ * caller has to zero in front: a second call on the same outputs gives the same bytes.  No workgroup ever waits for another.
+ * A NULL spec or out struct, a connectivity that is neither 4 nor 8, reserved != 0, a negative size, tile count or capacity,
+ * height * width above 2^30, max_edges or max_rings above 2^31, a NULL ids with something to read, NULL rings with
+ * max_rings > 0, NULL chain with rings wanted, a NULL work_device, or work_bytes below what dswx_outline_work_bytes returns:
+ * DSWX_ERR_ARG; ids, chain or rings off 4 bytes, or head or work_device off 8: DSWX_ERR_ALIGN.  (The arguments are checked
+ * before the context is, and a refused call writes nothing.)  The outputs and the working memory MUST NOT OVERLAP the input or
+ * each other: that is NOT CHECKED. */
+int dswx_outline_device(dswx_ctx_t* ctx, const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height,
+                        int64_t width, const dswx_outline_out_t* out_device, void* work_device, uint64_t work_bytes, void* stream);
+/* The same definition on HOST buffers as a plain scalar walk in C++: needs no device, no context and no working memory of the
+ * caller.  The other half of a comparison, not a fallback of the entry above.  The refusals of dswx_outline_device, except
+ * that every buffer may sit at any address. */
+int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                      const dswx_outline_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1107,7 +1196,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -45,7 +45,8 @@ EXPORTED_SYMBOLS = (
     'dswx_grid_device', 'dswx_batch_grid', 'dswx_grid_host',
     'dswx_label_device', 'dswx_batch_label', 'dswx_label_host',
     'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host',
-    'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host')
+    'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host',
+    'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -69,6 +70,8 @@ DISTANCE_NONE, DISTANCE_SUMMARY_WORDS, DISTANCE_MAX_WIDTH, DISTANCE_MAX_SIDE = 0
 # csrc/dswx_distance_rule.h: the rows and the columns of a column-pass thread, the columns of a block of the row pass and how far
 # the row pass looks to either side before it turns to the blocks (tests build shapes around the seams)
 DISTANCE_BAND_H, DISTANCE_COLS, DISTANCE_BLOCK_W, DISTANCE_NEAR = 64, 4, 64, 32
+HAS_OUTLINE = 1                   # DSWX_HAS_OUTLINE: additive to ABI v7
+OUTLINE_ROW_WORDS, OUTLINE_HEAD_WORDS = 8, 8
 
 
 class DswxError(RuntimeError):
@@ -274,9 +277,29 @@ class DistanceOut(ctypes.Structure):
         return cls(dist2 or None, nearest or None, within or None, summary or None)
 
 
+class OutlineSpec(ctypes.Structure):
+    """dswx_outline_spec_t; proteus_amd.outline.Spec is the Python form."""
+    _fields_ = [('max_edges', ctypes.c_int64), ('max_rings', ctypes.c_int64), ('connectivity', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+    @classmethod
+    def of(cls, spec):
+        return cls(spec.max_edges, spec.max_rings, spec.connectivity, 0)
+
+
+class OutlineOut(ctypes.Structure):
+    """dswx_outline_out_t: addresses, 0 / None = not wanted."""
+    _fields_ = [('chain', ctypes.c_void_p), ('rings', ctypes.c_void_p), ('head', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, chain=None, rings=None, head=None):
+        return cls(chain or None, rings or None, head or None)
+
+
 # the struct mirrors of the analytic entries by their C names (the offset tests compile the header against them)
 ANALYTIC_STRUCTS = {'dswx_label_spec_t': LabelSpec, 'dswx_label_out_t': LabelOut, 'dswx_body_spec_t': BodySpec,
-                    'dswx_body_out_t': BodyOut, 'dswx_distance_spec_t': DistanceSpec, 'dswx_distance_out_t': DistanceOut}
+                    'dswx_body_out_t': BodyOut, 'dswx_distance_spec_t': DistanceSpec, 'dswx_distance_out_t': DistanceOut,
+                    'dswx_outline_spec_t': OutlineSpec, 'dswx_outline_out_t': OutlineOut}
 
 COG_MAX_LEVELS = 8
 
@@ -463,6 +486,9 @@ def load_library(path=None):
         'dswx_body_table_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_body_table': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp, vp]),
         'dswx_body_table_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp]),
+        'dswx_outline_work_bytes': (ctypes.c_int, [vp, i64, i64, i64, vp]),
+        'dswx_outline_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, ctypes.c_uint64, vp]),
+        'dswx_outline_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -1076,6 +1102,42 @@ class Context:
                                                ctypes.byref(BodySpec.of(spec)), int(n_tiles), int(height), int(width),
                                                int(value_stride), ctypes.byref(out), ctypes.c_void_p(stream) if stream else None))
 
+    def outline_device(self, ids_ptr, spec, n_tiles, height, width, out, work_ptr, work_bytes, stream=None):
+        """dswx_outline_device: the regions of one device id plane uint32 [n_tiles][height * width] traced as rings by `spec`
+        (an outline.Spec; include/dswx_hip.h "outline", proteus_amd/outline.py states the definition in numpy) -> the outputs
+        `out` names (an OutlineOut of device addresses), with the caller's working memory of outline_work_bytes(...) bytes at
+        `work_ptr`; 9 + ceil(log2 capacity) launches and two memsets, asynchronous."""
+        _check(self.lib.dswx_outline_device(self.handle, ctypes.c_void_p(ids_ptr) if ids_ptr else None, ctypes.byref(OutlineSpec.of(spec)),
+                                            int(n_tiles), int(height), int(width), ctypes.byref(out),
+                                            ctypes.c_void_p(work_ptr) if work_ptr else None, int(work_bytes),
+                                            ctypes.c_void_p(stream) if stream else None))
+
+    def outline(self, ids, spec, n_tiles, height, width, want=('chain', 'rings', 'head'), stream=None):
+        """The regions of the device id plane uint32 [n_tiles][height * width] at `ids` (an address or a DeviceBuffer)
+        traced as rings: allocates the wanted outputs and the working memory (dswx_device_malloc), queues
+        dswx_outline_device on `stream` and waits for it, since the working memory is freed on return.  Returns {output:
+        DeviceBuffer}: 'chain' uint32 [n_tiles][max_edges], 'rings' uint32 [n_tiles][max_rings][8] (only with
+        spec.max_rings > 0), 'head' uint64 [n_tiles][8] -- device buffers owned by the caller."""
+        res = {}
+        for k in _outline_wanted(want, spec):
+            shape = _outline_shape(k, n_tiles, spec)
+            res[k] = self.malloc(max(int(np.prod(shape, dtype=np.int64)), 1) * np.dtype(OUTLINE_DTYPES[k]).itemsize)
+        work = None
+        try:
+            work_bytes = outline_work_bytes(spec, n_tiles, height, width)
+            work = self.malloc(work_bytes)
+            self.outline_device(getattr(ids, 'ptr', ids), spec, n_tiles, height, width, OutlineOut.of(**{k: b.ptr for k, b in res.items()}),
+                                work.ptr, work_bytes, stream)
+            self.synchronize(stream)
+        except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        finally:
+            if work is not None:
+                work.free()
+        return res
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -1340,6 +1402,50 @@ def body_table_host(label, value, spec, want=('dense', 'rows', 'head'), raster=N
     _check(load_library().dswx_body_table_host(_host_ptr(label) if label.size else None,
                                                _host_ptr(value) if value is not None else None,
                                                ctypes.byref(BodySpec.of(spec)), n, H, W, stride, ctypes.byref(out)))
+    return res
+
+
+OUTLINE_DTYPES = {'chain': np.uint32, 'rings': np.uint32, 'head': np.uint64}
+
+
+def _outline_wanted(want, spec):
+    """`want` in the order of the struct; 'rings' only with max_rings > 0, and only with 'chain'."""
+    want = tuple(want)
+    for k in want:
+        if k not in OUTLINE_DTYPES:
+            raise ValueError(f'unknown output {k!r} (chain, rings, head)')
+    if not want:
+        raise ValueError('no output wanted')
+    if spec.max_rings > 0 and 'rings' not in want:
+        raise ValueError(f"max_rings {spec.max_rings} without 'rings': a table that is not wanted has max_rings 0")
+    if 'rings' in want and spec.max_rings > 0 and 'chain' not in want:
+        raise ValueError("'rings' without 'chain': a row names a place in the chain")
+    return tuple(k for k in OUTLINE_DTYPES if k in want and (k != 'rings' or spec.max_rings > 0))
+
+
+def _outline_shape(k, n, spec):
+    return {'chain': (n, spec.max_edges), 'rings': (n, spec.max_rings, OUTLINE_ROW_WORDS), 'head': (n, OUTLINE_HEAD_WORDS)}[k]
+
+
+def outline_work_bytes(spec, n_tiles, height, width):
+    """dswx_outline_work_bytes (no device needed): the bytes of working memory dswx_outline_device needs."""
+    v = ctypes.c_uint64()
+    _check(load_library().dswx_outline_work_bytes(ctypes.byref(OutlineSpec.of(spec)), int(n_tiles), int(height), int(width), ctypes.byref(v)))
+    return int(v.value)
+
+
+def outline_host(ids, spec, want=('chain', 'rings', 'head')):
+    """dswx_outline_host (no device needed): the outputs of proteus_amd.outline.outline_tiles named in `want` -- 'rings' as
+    uint32 [n_tiles, max_rings, 8], which `.view(outline.ROW_DTYPE)[..., 0]` turns into records -- of a host id plane uint32
+    [n_tiles, H, W], by the library's scalar walk."""
+    ids = np.ascontiguousarray(ids)
+    if ids.dtype != np.uint32 or ids.ndim != 3:
+        raise ValueError(f'an id plane is uint32 [n_tiles, H, W], not {ids.dtype} {ids.shape}')
+    n, H, W = ids.shape
+    res = {k: np.zeros(_outline_shape(k, n, spec), dtype=OUTLINE_DTYPES[k]) for k in _outline_wanted(want, spec)}
+    out = OutlineOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_outline_host(_host_ptr(ids) if ids.size else None, ctypes.byref(OutlineSpec.of(spec)), n, H, W,
+                                            ctypes.byref(out)))
     return res
 
 
@@ -1697,6 +1803,25 @@ class DeviceBatch:
                                                       ctypes.c_void_p(getattr(label, 'ptr', label)), ctypes.byref(out),
                                                       ctypes.c_void_p(stream) if stream else None))
         except DswxError:
+            for buf in res.values():
+                buf.free()
+            raise
+        return res
+
+    def outline(self, name, label_spec, spec, tile0=0, n_tiles=None, stream=None):
+        """dswx_batch_label chained into dswx_outline_device: the bodies of tiles tile0 .. tile0 + n_tiles - 1 (default: every
+        tile from tile0) of the uint8 plane `name`, labelled by `label_spec` (a label.Spec) and traced as rings by `spec` (an
+        outline.Spec), on `stream`; complete on return.  Returns {output: DeviceBuffer}: 'chain' uint32
+        [n_tiles][max_edges], 'rings' uint32 [n_tiles][max_rings][8] (only with spec.max_rings > 0), 'head' uint64
+        [n_tiles][8] and 'label' uint32 [n_tiles][H*W] -- device planes owned by the caller.  (The library has no
+        dswx_batch_outline: the input of the outline is the caller's label plane, not a plane of the batch.)"""
+        if n_tiles == BATCH_ALL_TILES:
+            n_tiles = None
+        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        res = self.label(name, label_spec, tile0, n_tiles, want=('label',), stream=stream)
+        try:
+            res.update(self.ctx.outline(res['label'], spec, nt, self.height, self.width, stream=stream))
+        except (DswxError, ValueError):
             for buf in res.values():
                 buf.free()
             raise

@@ -293,6 +293,10 @@ int dswx_distance_check(const uint8_t* plane, const dswx_distance_spec_t* spec, 
 int dswx_distance_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height,
                          int64_t width, int64_t stride, const dswx_distance_out_t* out, hipStream_t s);
 
+// ---- outline (dswx_outline.hip): the launches for arguments that passed the checks of dswx_outline_device
+int dswx_outline_launch(dswx_ctx* ctx, const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height,
+                        int64_t width, const dswx_outline_out_t* out, void* work, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

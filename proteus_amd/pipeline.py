@@ -184,6 +184,36 @@ class DevicePlane:
             self.engine.ctx.synchronize()
         return made
 
+    def outline(self, label_spec, spec):
+        """The bodies of a [n, H, W] (or one [H, W]) uint8 plane labelled by `label_spec` (a label.Spec) and traced as rings
+        by `spec` (an outline.Spec), label chained into outline as the plane lies in HBM (dswx_label_device, then
+        dswx_outline_device; proteus_amd.outline.outline_tiles of the downloaded label plane gives the same): a dict of
+        DevicePlanes 'chain' uint32 [n, max_edges], 'rings' uint32 [n, max_rings, 8] (only with spec.max_rings > 0;
+        `.numpy().view(outline.ROW_DTYPE)[..., 0]` are the records), 'head' uint64 [n, 8] and 'label' uint32 [n, H, W], which
+        stay on the device.  With label_spec None this plane is itself a uint32 id plane and is traced as it is (no 'label'
+        then).  The working memory is taken for the call and given back."""
+        if label_spec is None:
+            if len(self.shape) not in (2, 3) or self.dtype != np.uint32:
+                raise ValueError(f'outlines are traced in a uint32 [n, H, W] or [H, W] id plane, not {self.dtype} {self.shape}')
+            made, ids = {}, self
+        else:
+            made = {'label': self.label(label_spec, want=('label',))['label']}
+            ids = made['label']
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        for k in _capi._outline_wanted(('chain', 'rings', 'head'), spec):
+            made[k] = self.engine.plane(_capi._outline_shape(k, n_tiles, spec), _capi.OUTLINE_DTYPES[k])
+        out = _capi.OutlineOut.of(**{k: p.ptr for k, p in made.items() if k != 'label'})
+        work_bytes = _capi.outline_work_bytes(spec, n_tiles, height, width)
+        work = self.engine._take(work_bytes)
+        try:
+            with self.engine.lock, stages.span('gpu: outline'):
+                self.engine.ctx.outline_device(ids.ptr, spec, n_tiles, height, width, out, work.ptr, work_bytes)
+                self.engine.ctx.synchronize()
+        finally:
+            self.engine._give(work)
+        return made
+
     def body_table(self, spec, value=None, want=('dense', 'rows', 'head')):
         """The bodies of this LABEL plane -- uint32 [n, H, W] (or one [H, W]) as label(...)['label'] leaves it in HBM --
         renumbered 1 .. K and tabulated (dswx_body_table_device; proteus_amd.bodies.body_table of the same arrays gives the
