@@ -3,6 +3,7 @@
 There is exactly one compute path: the HIP library.  If it is missing, or no
 MI355X is visible, every entry point here raises -- nothing falls back to numpy.
 """
+import contextlib
 import ctypes
 import threading
 import weakref
@@ -674,6 +675,51 @@ def _host_ptr(arr):
     return ctypes.c_void_p(arr.ctypes.data)
 
 
+def _stream_arg(stream):
+    """The `stream` argument of an entry: the caller's hipStream_t, NULL (the context's own stream) for None or 0."""
+    return ctypes.c_void_p(stream) if stream else None
+
+
+def _wanted(want, known):
+    """`want` as a tuple: not empty, every name one of `known` (the outputs of an entry in the order of its struct)."""
+    want = tuple(want)
+    for k in want:
+        if k not in known:
+            raise ValueError(f'unknown output {k!r} ({", ".join(known)})')
+    if not want:
+        raise ValueError('no output wanted')
+    return want
+
+
+def _host_plane(tiles, raster):
+    """(tiles, n_tiles, H, W, tile_stride) of a host plane: uint8 [n_tiles, H, W] (stride 0 = packed), or with raster=(H, W) a
+    padded plane [n_tiles, tile_stride]."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
+    if raster is None:
+        (n, H, W), stride = tiles.shape, 0
+    else:
+        (n, stride), (H, W) = tiles.shape, raster
+    return tiles, n, H, W, stride
+
+
+def _malloc_planes(ctx, planes):
+    """{name: DeviceBuffer} for {name: (shape, dtype)}; an empty plane still has an address."""
+    return {k: ctx.malloc(max(int(np.prod(shape, dtype=np.int64)), 1) * np.dtype(dt).itemsize) for k, (shape, dt) in planes.items()}
+
+
+@contextlib.contextmanager
+def _owned(res, errors=None):
+    """The device buffers of `res` were allocated for the call made inside: the caller's when it succeeds, freed when it raises."""
+    try:
+        yield res
+    except errors or DswxError:
+        for buf in res.values():
+            buf.free()
+        raise
+
+
 class DeviceBuffer:
     """A hipMalloc'ed span owned by a Context."""
 
@@ -859,7 +905,7 @@ class Context:
             self.handle, ctypes.byref(params), int(n_tiles), int(n_pixels),
             ctypes.byref(pin), ctypes.byref(pout),
             ctypes.c_void_p(counters_ptr) if counters_ptr else None,
-            ctypes.c_void_p(stream) if stream else None))
+            _stream_arg(stream)))
 
     def interpret_layer(self, diag_decimal):
         """generate_interpreted_layer on the device; any integer array in, uint8 out."""
@@ -915,7 +961,7 @@ class Context:
         _check(self.lib.dswx_landcover_mask_batch(
             self.handle, ctypes.c_void_p(wc_ptr), ctypes.c_void_p(cg_ptr), int(n_tiles), int(height),
             int(width), _host_ptr(fc) if fc.size else None, int(fc.size), _host_ptr(thr),
-            int(year_offset), ctypes.c_void_p(out_ptr), int(out_tile_stride), ctypes.c_void_p(stream) if stream else None))
+            int(year_offset), ctypes.c_void_p(out_ptr), int(out_tile_stride), _stream_arg(stream)))
 
     def shadow_layer_device(self, dem_ptr, n_tiles, height, width, margin, sun_vector, sin_azimuth,
                             cos_azimuth, min_slope_angle, max_sun_local_inc_angle, out_ptr,
@@ -930,14 +976,14 @@ class Context:
                 self.handle, ctypes.c_void_p(dem_ptr), int(n_tiles), int(height), int(width), int(margin), ctypes.byref(vec),
                 float(sin_azimuth), float(cos_azimuth), float(slope_arg_max), float(inc_q_min), int(bool(float32)),
                 float(pixel_spacing_x), float(pixel_spacing_y), ctypes.c_void_p(out_ptr), int(out_tile_stride),
-                ctypes.c_void_p(stream) if stream else None))
+                _stream_arg(stream)))
             return
         fn = self.lib.dswx_shadow_layer_device_q32 if float32 else self.lib.dswx_shadow_layer_device_q
         _check(fn(
             self.handle, ctypes.c_void_p(dem_ptr), int(n_tiles), int(height), int(width), int(margin),
             ctypes.byref(vec), float(sin_azimuth), float(cos_azimuth), slope_arg_max, inc_q_min,
             float(pixel_spacing_x), float(pixel_spacing_y),
-            ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None))
+            ctypes.c_void_p(out_ptr), _stream_arg(stream)))
 
     # ---- libdswx_lab.so (experiments; tools/ and the variant tests only) -----------
     def lab_configure(self, **settings):
@@ -953,18 +999,18 @@ class Context:
     def stream_probe(self, n_tiles, n_pixels, pin, pout, variant=0, stream=None, tile_stride=0):
         _check(load_lab().dswx_stream_probe(
             self.handle, int(n_tiles), int(n_pixels), int(tile_stride), ctypes.byref(pin),
-            ctypes.byref(pout), int(variant), ctypes.c_void_p(stream) if stream else None))
+            ctypes.byref(pout), int(variant), _stream_arg(stream)))
 
     def classify_batch(self, params, geom, pin, pout, counters_ptr=None, stream=None):
         _check(self.lib.dswx_classify_batch(
             self.handle, ctypes.byref(params), ctypes.byref(geom), ctypes.byref(pin),
             ctypes.byref(pout), ctypes.c_void_p(counters_ptr) if counters_ptr else None,
-            ctypes.c_void_p(stream) if stream else None))
+            _stream_arg(stream)))
 
     def synth_batch(self, seed, tile0, geom, pin, stream=None):
         _check(self.lib.dswx_synth_batch(
             self.handle, int(seed), int(tile0), ctypes.byref(geom), ctypes.byref(pin),
-            ctypes.c_void_p(stream) if stream else None))
+            _stream_arg(stream)))
 
     def classify_device_2d(self, params, n_tiles, height, width, pin, pout, counters_ptr=None,
                            stream=None):
@@ -972,12 +1018,12 @@ class Context:
             self.handle, ctypes.byref(params), int(n_tiles), int(height), int(width),
             ctypes.byref(pin), ctypes.byref(pout),
             ctypes.c_void_p(counters_ptr) if counters_ptr else None,
-            ctypes.c_void_p(stream) if stream else None))
+            _stream_arg(stream)))
 
     def synth_fill(self, seed, tile0, n_tiles, height, width, pin, stream=None):
         _check(self.lib.dswx_synth_fill(
             self.handle, int(seed), int(tile0), int(n_tiles), int(height), int(width),
-            ctypes.byref(pin), ctypes.c_void_p(stream) if stream else None))
+            ctypes.byref(pin), _stream_arg(stream)))
 
     def malloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
@@ -988,12 +1034,12 @@ class Context:
         f = (ctypes.c_int32 * max(len(factors), 1))(*[int(x) for x in factors])
         _check(self.lib.dswx_cog_blocks_device(self.handle, ctypes.c_void_p(plane_ptr), int(elem_bytes), int(height), int(width),
                                                int(tile), f, len(factors), int(predictor), ctypes.c_void_p(blocks_ptr),
-                                               ctypes.c_void_p(stream) if stream else None))
+                                               _stream_arg(stream)))
 
     def untile_device(self, blocks_ptr, elem_bytes, height, width, block_width, block_height, predictor, plane_ptr, stream=None):
         _check(self.lib.dswx_untile_device(self.handle, ctypes.c_void_p(blocks_ptr), int(elem_bytes), int(height), int(width),
                                            int(block_width), int(block_height), int(predictor), ctypes.c_void_p(plane_ptr),
-                                           ctypes.c_void_p(stream) if stream else None))
+                                           _stream_arg(stream)))
 
     def rgb_planes_device(self, red_ptr, green_ptr, blue_ptr, diag_ptr, n_pixels, scale, offset, clip, out_ptr, stream=None):
         sc = (ctypes.c_double * 3)(*[float(v) for v in scale])
@@ -1001,7 +1047,7 @@ class Context:
         _check(self.lib.dswx_rgb_planes_device(self.handle, ctypes.c_void_p(red_ptr), ctypes.c_void_p(green_ptr),
                                                ctypes.c_void_p(blue_ptr), ctypes.c_void_p(diag_ptr) if diag_ptr else None,
                                                int(n_pixels), ctypes.byref(sc), ctypes.byref(of), int(bool(clip)),
-                                               ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None))
+                                               ctypes.c_void_p(out_ptr), _stream_arg(stream)))
 
     def convolve_axis_device(self, src_ptr, src_is_f64, n_lines, n_in, src_line_stride, src_elem_stride, n_out, taps, first_ptr,
                              weights_ptr, dst_ptr, dst_is_f64, dst_line_stride, dst_elem_stride, stream=None):
@@ -1009,31 +1055,31 @@ class Context:
             self.handle, ctypes.c_void_p(src_ptr), int(bool(src_is_f64)), int(n_lines), int(n_in), int(src_line_stride),
             int(src_elem_stride), int(n_out), int(taps), ctypes.c_void_p(first_ptr), ctypes.c_void_p(weights_ptr),
             ctypes.c_void_p(dst_ptr), int(bool(dst_is_f64)), int(dst_line_stride), int(dst_elem_stride),
-            ctypes.c_void_p(stream) if stream else None))
+            _stream_arg(stream)))
 
     def to_byte_device(self, src_ptr, src_dtype, n, dst_ptr, stream=None):
         kind = {'uint16': 1, 'int16': 2, 'float32': 3}.get(np.dtype(src_dtype).name)
         if kind is None:
             raise ValueError(f'to_byte_device: {np.dtype(src_dtype)} planes are not taken')
         _check(self.lib.dswx_to_byte_device(self.handle, ctypes.c_void_p(src_ptr), kind, int(n), ctypes.c_void_p(dst_ptr),
-                                            ctypes.c_void_p(stream) if stream else None))
+                                            _stream_arg(stream)))
 
     def gather_2d_device(self, src_ptr, elem_bytes, src_height, src_width, rows_ptr, n_rows, cols_ptr, n_cols, dst_ptr, stream=None):
         _check(self.lib.dswx_gather_2d_device(self.handle, ctypes.c_void_p(src_ptr), int(elem_bytes), int(src_height), int(src_width),
                                               ctypes.c_void_p(rows_ptr), int(n_rows), ctypes.c_void_p(cols_ptr), int(n_cols),
-                                              ctypes.c_void_p(dst_ptr), ctypes.c_void_p(stream) if stream else None))
+                                              ctypes.c_void_p(dst_ptr), _stream_arg(stream)))
 
     def copy_2d_device(self, dst_ptr, dst_pitch, src_ptr, src_pitch, width_bytes, height, stream=None):
         _check(self.lib.dswx_copy_2d_device(self.handle, ctypes.c_void_p(dst_ptr), int(dst_pitch), ctypes.c_void_p(src_ptr),
                                             int(src_pitch), int(width_bytes), int(height),
-                                            ctypes.c_void_p(stream) if stream else None))
+                                            _stream_arg(stream)))
 
     def checksum_device(self, plane_ptr, elem_bytes, n_tiles, n_elems, out_ptr, tile_stride=0, stream=None):
         """dswx_checksum_device: the per-tile checksums (include/dswx_hip.h "checksums"; proteus_amd/checksum.py states the
         definition in numpy) of one device plane [n_tiles][tile_stride] -> device uint64 [n_tiles] at out_ptr; asynchronous."""
         _check(self.lib.dswx_checksum_device(self.handle, ctypes.c_void_p(plane_ptr), int(elem_bytes), int(n_tiles), int(n_elems),
                                              int(tile_stride), ctypes.c_void_p(out_ptr),
-                                             ctypes.c_void_p(stream) if stream else None))
+                                             _stream_arg(stream)))
 
     def compare_device(self, a_ptr, b_ptr, kind, n_tiles, n_elems, out_ptr, a_stride=0, b_stride=0, atol=0.0, rtol=0.0,
                        equal_nan=True, stream=None):
@@ -1043,14 +1089,14 @@ class Context:
         _check(self.lib.dswx_compare_device(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr), int(kind), int(n_tiles),
                                             int(n_elems), int(a_stride), int(b_stride), float(atol), float(rtol),
                                             int(bool(equal_nan)), ctypes.c_void_p(out_ptr),
-                                            ctypes.c_void_p(stream) if stream else None))
+                                            _stream_arg(stream)))
 
     def histogram_device(self, plane_ptr, kind, n_tiles, n_elems, out_ptr, lo=0, shift=0, tile_stride=0, stream=None):
         """dswx_histogram_device: one device plane [n_tiles][tile_stride] of one kind (HIST_*; include/dswx_hip.h "histogram",
         proteus_amd/histogram.py states the definition in numpy) -> device uint64 [n_tiles][256] at out_ptr; asynchronous."""
         _check(self.lib.dswx_histogram_device(self.handle, ctypes.c_void_p(plane_ptr), int(kind), int(lo), int(shift), int(n_tiles),
                                               int(n_elems), int(tile_stride), ctypes.c_void_p(out_ptr),
-                                              ctypes.c_void_p(stream) if stream else None))
+                                              _stream_arg(stream)))
 
     def crosstab_device(self, a_ptr, b_ptr, spec, n_tiles, n_elems, out_ptr, a_stride=0, b_stride=0, stream=None):
         """dswx_crosstab_device: device planes a [n_tiles][a_stride] (of spec.a_kind) and b [n_tiles][b_stride] (uint8)
@@ -1058,7 +1104,7 @@ class Context:
         definition in numpy) -> device uint64 [n_tiles][256] at out_ptr; asynchronous."""
         _check(self.lib.dswx_crosstab_device(self.handle, ctypes.c_void_p(a_ptr), ctypes.c_void_p(b_ptr),
                                              ctypes.byref(CrosstabSpec.of(spec)), int(n_tiles), int(n_elems), int(a_stride),
-                                             int(b_stride), ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream) if stream else None))
+                                             int(b_stride), ctypes.c_void_p(out_ptr), _stream_arg(stream)))
 
     def stack_device(self, stack_ptr, spec, n_tiles, n_elems, out, tile_stride=0, stream=None):
         """dswx_stack_device: one device stack uint8 [n_tiles][tile_stride] composited per pixel by `spec` (a stack.Spec;
@@ -1066,7 +1112,7 @@ class Context:
         of device addresses, n_elems elements each); one launch, asynchronous."""
         _check(self.lib.dswx_stack_device(self.handle, ctypes.c_void_p(stack_ptr), ctypes.byref(StackSpec.of(spec)), int(n_tiles),
                                           int(n_elems), int(tile_stride), ctypes.byref(out),
-                                          ctypes.c_void_p(stream) if stream else None))
+                                          _stream_arg(stream)))
 
     def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
@@ -1074,7 +1120,7 @@ class Context:
         the planes `out` names (a GridOut of device addresses, n_tiles x GH x GW elements each); one launch, asynchronous."""
         _check(self.lib.dswx_grid_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(GridSpec.of(spec)), int(n_tiles),
                                          int(height), int(width), int(tile_stride), ctypes.byref(out),
-                                         ctypes.c_void_p(stream) if stream else None))
+                                         _stream_arg(stream)))
 
     def label_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_label_device: the connected bodies of one device plane uint8 [n_tiles][tile_stride], every tile a height x
@@ -1082,7 +1128,7 @@ class Context:
         numpy) -> the planes `out` names (a LabelOut of device addresses); a fixed number of launches, asynchronous."""
         _check(self.lib.dswx_label_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(LabelSpec.of(spec)), int(n_tiles),
                                           int(height), int(width), int(tile_stride), ctypes.byref(out),
-                                          ctypes.c_void_p(stream) if stream else None))
+                                          _stream_arg(stream)))
 
     def distance_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_distance_device: the squared distance of every pixel of one device plane uint8 [n_tiles][tile_stride], every
@@ -1091,7 +1137,7 @@ class Context:
         a fixed number of launches, asynchronous."""
         _check(self.lib.dswx_distance_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(DistanceSpec.of(spec)), int(n_tiles),
                                              int(height), int(width), int(tile_stride), ctypes.byref(out),
-                                             ctypes.c_void_p(stream) if stream else None))
+                                             _stream_arg(stream)))
 
     def body_table_device(self, label_ptr, value_ptr, spec, n_tiles, height, width, out, value_stride=0, stream=None):
         """dswx_body_table_device: the bodies of one device label plane uint32 [n_tiles][height * width] renumbered and
@@ -1100,7 +1146,7 @@ class Context:
         outputs `out` names (a BodyOut of device addresses); four launches and two memsets, asynchronous."""
         _check(self.lib.dswx_body_table_device(self.handle, ctypes.c_void_p(label_ptr), ctypes.c_void_p(value_ptr) if value_ptr else None,
                                                ctypes.byref(BodySpec.of(spec)), int(n_tiles), int(height), int(width),
-                                               int(value_stride), ctypes.byref(out), ctypes.c_void_p(stream) if stream else None))
+                                               int(value_stride), ctypes.byref(out), _stream_arg(stream)))
 
     def outline_device(self, ids_ptr, spec, n_tiles, height, width, out, work_ptr, work_bytes, stream=None):
         """dswx_outline_device: the regions of one device id plane uint32 [n_tiles][height * width] traced as rings by `spec`
@@ -1110,7 +1156,7 @@ class Context:
         _check(self.lib.dswx_outline_device(self.handle, ctypes.c_void_p(ids_ptr) if ids_ptr else None, ctypes.byref(OutlineSpec.of(spec)),
                                             int(n_tiles), int(height), int(width), ctypes.byref(out),
                                             ctypes.c_void_p(work_ptr) if work_ptr else None, int(work_bytes),
-                                            ctypes.c_void_p(stream) if stream else None))
+                                            _stream_arg(stream)))
 
     def outline(self, ids, spec, n_tiles, height, width, want=('chain', 'rings', 'head'), stream=None):
         """The regions of the device id plane uint32 [n_tiles][height * width] at `ids` (an address or a DeviceBuffer)
@@ -1118,21 +1164,15 @@ class Context:
         dswx_outline_device on `stream` and waits for it, since the working memory is freed on return.  Returns {output:
         DeviceBuffer}: 'chain' uint32 [n_tiles][max_edges], 'rings' uint32 [n_tiles][max_rings][8] (only with
         spec.max_rings > 0), 'head' uint64 [n_tiles][8] -- device buffers owned by the caller."""
-        res = {}
-        for k in _outline_wanted(want, spec):
-            shape = _outline_shape(k, n_tiles, spec)
-            res[k] = self.malloc(max(int(np.prod(shape, dtype=np.int64)), 1) * np.dtype(OUTLINE_DTYPES[k]).itemsize)
+        res = _malloc_planes(self, {k: (_outline_shape(k, n_tiles, spec), OUTLINE_DTYPES[k]) for k in _outline_wanted(want, spec)})
         work = None
         try:
-            work_bytes = outline_work_bytes(spec, n_tiles, height, width)
-            work = self.malloc(work_bytes)
-            self.outline_device(getattr(ids, 'ptr', ids), spec, n_tiles, height, width, OutlineOut.of(**{k: b.ptr for k, b in res.items()}),
-                                work.ptr, work_bytes, stream)
-            self.synchronize(stream)
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+            with _owned(res):
+                work_bytes = outline_work_bytes(spec, n_tiles, height, width)
+                work = self.malloc(work_bytes)
+                self.outline_device(getattr(ids, 'ptr', ids), spec, n_tiles, height, width, OutlineOut.of(**{k: b.ptr for k, b in res.items()}),
+                                    work.ptr, work_bytes, stream)
+                self.synchronize(stream)
         finally:
             if work is not None:
                 work.free()
@@ -1141,16 +1181,16 @@ class Context:
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
-                                              ctypes.c_void_p(stream) if stream else None))
+                                              _stream_arg(stream)))
 
     def d2h_async(self, host_arr, src_ptr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_d2h_async(self.handle, _host_ptr(host_arr), ctypes.c_void_p(src_ptr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
-                                              ctypes.c_void_p(stream) if stream else None))
+                                              _stream_arg(stream)))
 
     def synchronize(self, stream=None):
         _check(self.lib.dswx_stream_synchronize(
-            self.handle, ctypes.c_void_p(stream) if stream else None))
+            self.handle, _stream_arg(stream)))
 
     def event(self):
         e = ctypes.c_void_p()
@@ -1159,7 +1199,7 @@ class Context:
 
     def record(self, event, stream=None):
         _check(self.lib.dswx_event_record(
-            self.handle, event, ctypes.c_void_p(stream) if stream else None))
+            self.handle, event, _stream_arg(stream)))
 
     def elapsed_ms(self, start, stop):
         ms = ctypes.c_float()
@@ -1242,12 +1282,7 @@ def stack_host(tiles, spec, want=('count', 'last', 'last_index', 'share')):
 def _stack_planes(want, spec, shape, make):
     """{name: plane} for the outputs named in `want` ('count' is [n_cats, ...]), each made by make(shape, dtype)."""
     dtypes = {'count': np.uint16, 'last': np.uint8, 'last_index': np.uint16, 'share': np.uint8}
-    want = tuple(want)
-    for k in want:
-        if k not in dtypes:
-            raise ValueError(f'unknown output {k!r} (count, last, last_index, share)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, dtypes)
     return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
 
 
@@ -1255,13 +1290,7 @@ def grid_host(tiles, spec, want=('count', 'share', 'coverage', 'major'), raster=
     """dswx_grid_host (no device needed): the planes of proteus_amd.grid.grid_tiles -- those named in `want` -- of a host
     plane uint8 [n_tiles, H, W], by the library's scalar statement of the definition.  With raster=(H, W), `tiles` is a padded
     plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
-    tiles = np.ascontiguousarray(tiles)
-    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
-        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
-    if raster is None:
-        (n, H, W), stride = tiles.shape, 0
-    else:
-        (n, stride), (H, W) = tiles.shape, raster
+    tiles, n, H, W, stride = _host_plane(tiles, raster)
     from .grid import grid_shape
     res = _grid_planes(want, spec, (n,) + grid_shape(H, W, spec), lambda shp, dt: np.zeros(shp, dtype=dt))
     out = GridOut.of(count=[c.ctypes.data for c in res['count']] if 'count' in res else (),
@@ -1274,12 +1303,7 @@ def grid_host(tiles, spec, want=('count', 'share', 'coverage', 'major'), raster=
 def _grid_planes(want, spec, shape, make):
     """{name: plane} for the outputs named in `want` ('count' is [n_cats, ...]), each made by make(shape, dtype)."""
     dtypes = {'count': np.uint32, 'share': np.uint8, 'coverage': np.uint8, 'major': np.uint8}
-    want = tuple(want)
-    for k in want:
-        if k not in dtypes:
-            raise ValueError(f'unknown output {k!r} (count, share, coverage, major)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, dtypes)
     return {k: make(((spec.n_cats,) if k == 'count' else ()) + tuple(shape), dtypes[k]) for k in dtypes if k in want}
 
 
@@ -1288,12 +1312,7 @@ LABEL_DTYPES = {'label': np.uint32, 'size': np.uint32, 'sieved': np.uint8, 'summ
 
 def _label_wanted(want):
     """`want` in the order of the struct; 'label' is always made (it is the working array), 'size' with sieved or summary."""
-    want = tuple(want)
-    for k in want:
-        if k not in LABEL_DTYPES:
-            raise ValueError(f'unknown output {k!r} (label, size, sieved, summary)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, LABEL_DTYPES)
     made = {'label'} | set(want) | ({'size'} if 'sieved' in want or 'summary' in want else set())
     return tuple(k for k in LABEL_DTYPES if k in made)
 
@@ -1302,13 +1321,7 @@ def label_host(tiles, spec, want=('label', 'size', 'sieved', 'summary'), raster=
     """dswx_label_host (no device needed): the planes of proteus_amd.label.label_tiles -- those named in `want`, and the ones
     they need -- of a host plane uint8 [n_tiles, H, W], by the library's scalar union-find.  With raster=(H, W), `tiles` is a
     padded plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
-    tiles = np.ascontiguousarray(tiles)
-    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
-        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
-    if raster is None:
-        (n, H, W), stride = tiles.shape, 0
-    else:
-        (n, stride), (H, W) = tiles.shape, raster
+    tiles, n, H, W, stride = _host_plane(tiles, raster)
     res = {k: np.zeros((n, LABEL_SUMMARY_WORDS) if k == 'summary' else (n, H, W), dtype=LABEL_DTYPES[k]) for k in _label_wanted(want)}
     out = LabelOut.of(**{k: a.ctypes.data for k, a in res.items()})
     _check(load_library().dswx_label_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(LabelSpec.of(spec)), n, H, W,
@@ -1321,12 +1334,7 @@ DISTANCE_DTYPES = {'dist2': np.uint32, 'nearest': np.uint32, 'within': np.uint8,
 
 def _distance_wanted(want, spec):
     """`want` in the order of the struct; 'dist2' is always made (it is the working array); 'within' needs a radius."""
-    want = tuple(want)
-    for k in want:
-        if k not in DISTANCE_DTYPES:
-            raise ValueError(f'unknown output {k!r} (dist2, nearest, within, summary)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, DISTANCE_DTYPES)
     if 'within' in want and spec.max_radius == 0:
         raise ValueError("'within' is wanted but max_radius is 0: the ring needs a radius")
     return tuple(k for k in DISTANCE_DTYPES if k == 'dist2' or k in want)
@@ -1344,13 +1352,7 @@ def distance_host(tiles, spec, want=('dist2', 'nearest', 'summary'), raster=None
     """dswx_distance_host (no device needed): the planes of proteus_amd.distance.distance_tiles -- those named in `want`, and
     'dist2' always -- of a host plane uint8 [n_tiles, H, W], by the library's scalar transform.  With raster=(H, W), `tiles`
     is a padded plane uint8 [n_tiles, tile_stride], tile_stride >= H * W, whose padding is not read."""
-    tiles = np.ascontiguousarray(tiles)
-    if tiles.dtype != np.uint8 or tiles.ndim != (3 if raster is None else 2):
-        raise ValueError(f'a plane is uint8 [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride], not {tiles.dtype} {tiles.shape}')
-    if raster is None:
-        (n, H, W), stride = tiles.shape, 0
-    else:
-        (n, stride), (H, W) = tiles.shape, raster
+    tiles, n, H, W, stride = _host_plane(tiles, raster)
     _distance_refuse(H, W)
     res = {k: np.zeros((n, DISTANCE_SUMMARY_WORDS) if k == 'summary' else (n, H, W), dtype=DISTANCE_DTYPES[k])
            for k in _distance_wanted(want, spec)}
@@ -1365,12 +1367,7 @@ BODY_DTYPES = {'dense': np.uint32, 'rows': np.uint32, 'head': np.uint64}
 
 def _body_wanted(want, spec):
     """`want` in the order of the struct; 'dense' is always made (it is the working array); 'rows' only with max_rows > 0."""
-    want = tuple(want)
-    for k in want:
-        if k not in BODY_DTYPES:
-            raise ValueError(f'unknown output {k!r} (dense, rows, head)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, BODY_DTYPES)
     if spec.max_rows > 0 and 'rows' not in want:
         raise ValueError(f"max_rows {spec.max_rows} without 'rows': a table that is not wanted has max_rows 0")
     return tuple(k for k in BODY_DTYPES if k == 'dense' or (k in want and (k != 'rows' or spec.max_rows > 0)))
@@ -1410,12 +1407,7 @@ OUTLINE_DTYPES = {'chain': np.uint32, 'rings': np.uint32, 'head': np.uint64}
 
 def _outline_wanted(want, spec):
     """`want` in the order of the struct; 'rings' only with max_rings > 0, and only with 'chain'."""
-    want = tuple(want)
-    for k in want:
-        if k not in OUTLINE_DTYPES:
-            raise ValueError(f'unknown output {k!r} (chain, rings, head)')
-    if not want:
-        raise ValueError('no output wanted')
+    want = _wanted(want, OUTLINE_DTYPES)
     if spec.max_rings > 0 and 'rings' not in want:
         raise ValueError(f"max_rings {spec.max_rings} without 'rings': a table that is not wanted has max_rings 0")
     if 'rings' in want and spec.max_rings > 0 and 'chain' not in want:
@@ -1482,6 +1474,13 @@ def _batch_flags(masks, extra_layers, separate_outputs, sliding_outputs=False):
     return ((BATCH_MASKS if masks else 0) | (BATCH_WTR1_AEROSOL if 'wtr1_aerosol' in extra_layers else 0)
             | (BATCH_BROWSE if 'browse' in extra_layers else 0) | (BATCH_SEPARATE_OUTPUTS if separate_outputs else 0)
             | (BATCH_SLIDING_OUTPUTS if sliding_outputs else 0))
+
+
+def _plane_index(name):
+    """DSWX_PLANE_* of a plane by its name."""
+    if name not in PLANE_INDEX:
+        raise ValueError(f'unknown plane {name!r}')
+    return PLANE_INDEX[name]
 
 
 class DeviceBatch:
@@ -1568,7 +1567,7 @@ class DeviceBatch:
 
     def synth(self, seed, tile0=0, stream=None):
         _check(self.ctx.lib.dswx_batch_synth(self.handle, int(seed), int(tile0),
-                                             ctypes.c_void_p(stream) if stream else None))
+                                             _stream_arg(stream)))
 
     def classify(self, params, stream=None, counters=True, n_tiles=None):
         """The first `n_tiles` resident tiles (None = all, DSWX_BATCH_ALL_TILES; 0 = none: an empty chunk is no work).
@@ -1577,7 +1576,7 @@ class DeviceBatch:
             n_tiles = BATCH_ALL_TILES
         if counters:
             _check(self.ctx.lib.dswx_batch_classify(self.handle, ctypes.byref(params), int(n_tiles),
-                                                    ctypes.c_void_p(stream) if stream else None))
+                                                    _stream_arg(stream)))
         elif n_tiles != 0:
             geom = BatchGeom(self.n_tiles if n_tiles == BATCH_ALL_TILES else n_tiles, self.height, self.width,
                              self.tile_stride)
@@ -1602,40 +1601,43 @@ class DeviceBatch:
             getattr(self.pout, n) if n == 'diag' or n in U8_LAYERS else
             self.pin.band[BAND_NAMES.index(n)] if n in BAND_NAMES else getattr(self.pin, n))]
 
+    def _mask(self, names):
+        """(plane mask, the names in the order of its bits: row i of a mask entry's output is plane order[i]) of `names`
+        (None: every plane the batch has)."""
+        names = self.plane_names() if names is None else list(names)
+        mask = 0
+        for n in names:
+            mask |= 1 << _plane_index(n)
+        return mask, sorted(set(names), key=PLANE_INDEX.get)
+
+    def _tiles(self, tile0, n_tiles):
+        """(the n_tiles an entry is given, the tiles its outputs are sized for) for tiles tile0 .. tile0 + n_tiles - 1; None
+        is DSWX_BATCH_ALL_TILES: every tile from tile0, which the library resolves."""
+        if n_tiles is None or n_tiles == BATCH_ALL_TILES:
+            return BATCH_ALL_TILES, max(self.n_tiles - tile0, 0)
+        return int(n_tiles), max(int(n_tiles), 0)
+
     def checksums(self, names=None, tile0=0, n_tiles=None, stream=None):
         """dswx_batch_checksum: {name: uint64 [n_tiles]}, the checksum of every selected plane of tiles tile0 .. tile0 +
         n_tiles - 1 (default: every plane the batch has -- 'counters' only when named -- and every tile from tile0), by ONE
         kernel launch; complete on return.  proteus_amd.checksum.checksum(read_tile(name, t)) is the same number."""
-        names = self.plane_names() if names is None else list(names)
-        mask = 0
-        for n in names:
-            if n not in PLANE_INDEX:
-                raise ValueError(f'unknown plane {n!r}')
-            mask |= 1 << PLANE_INDEX[n]
-        n_tiles = self.n_tiles - tile0 if n_tiles is None else n_tiles
-        order = sorted(set(names), key=PLANE_INDEX.get)
-        out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=np.uint64)
-        _check(self.ctx.lib.dswx_batch_checksum(self.handle, mask, int(tile0), int(n_tiles), _host_ptr(out),
-                                                ctypes.c_void_p(stream) if stream else None))
-        return {n: out[i] for i, n in enumerate(order)}
+        mask, order = self._mask(names)
+        n_tiles, count = self._tiles(tile0, n_tiles)
+        out = np.zeros((len(order), count), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_checksum(self.handle, mask, int(tile0), n_tiles, _host_ptr(out), _stream_arg(stream)))
+        return dict(zip(order, out))
 
     def compare(self, other, names=None, tile0=0, n_tiles=None, atol=0.0, rtol=0.0, equal_nan=True, stream=None):
         """dswx_batch_compare: {name: compare.RECORD [n_tiles]}, this batch's selected planes against `other`'s (default:
         every plane this batch has), tiles tile0 .. tile0 + n_tiles - 1 of both, by ONE kernel launch; complete on return.
         proteus_amd.compare.compare(self.read_tile(name, t), other.read_tile(name, t), ...) is the same record."""
         from .compare import RECORD
-        names = self.plane_names() if names is None else list(names)
-        mask = 0
-        for n in names:
-            if n not in PLANE_INDEX:
-                raise ValueError(f'unknown plane {n!r}')
-            mask |= 1 << PLANE_INDEX[n]
-        n_tiles = self.n_tiles - tile0 if n_tiles is None else n_tiles
-        order = sorted(set(names), key=PLANE_INDEX.get)
-        out = np.zeros((len(order), max(int(n_tiles), 0)), dtype=RECORD)
-        _check(self.ctx.lib.dswx_batch_compare(self.handle, other.handle, mask, int(tile0), int(n_tiles), float(atol), float(rtol),
-                                               int(bool(equal_nan)), _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
-        return {n: out[i] for i, n in enumerate(order)}
+        mask, order = self._mask(names)
+        n_tiles, count = self._tiles(tile0, n_tiles)
+        out = np.zeros((len(order), count), dtype=RECORD)
+        _check(self.ctx.lib.dswx_batch_compare(self.handle, other.handle, mask, int(tile0), n_tiles, float(atol), float(rtol),
+                                               int(bool(equal_nan)), _host_ptr(out), _stream_arg(stream)))
+        return dict(zip(order, out))
 
     def histogram(self, names=None, tile0=0, n_tiles=None, band_lo=0, band_shift=6, stream=None):
         """dswx_batch_histogram: {name: uint64 [n_tiles, 256]}, the counts of every selected plane of tiles tile0 .. tile0 +
@@ -1643,20 +1645,12 @@ class DeviceBatch:
         The bands are binned linearly with band_lo / band_shift (the defaults: reflectances 0 .. 16383 in bins of 64), 'diag' by
         its five test bits, every other plane by its byte: proteus_amd.histogram.histogram(read_tile(name, t), kind, lo, shift)
         is the same record."""
-        names = self.plane_names() if names is None else list(names)
-        mask = 0
-        for n in names:
-            if n not in PLANE_INDEX:
-                raise ValueError(f'unknown plane {n!r}')
-            mask |= 1 << PLANE_INDEX[n]
-        if n_tiles is None:
-            n_tiles = BATCH_ALL_TILES
-        count = self.n_tiles - tile0 if n_tiles == BATCH_ALL_TILES else n_tiles
-        order = sorted(set(names), key=PLANE_INDEX.get)
-        out = np.zeros((len(order), max(int(count), 0), HIST_BINS), dtype=np.uint64)
-        _check(self.ctx.lib.dswx_batch_histogram(self.handle, mask, int(tile0), int(n_tiles), int(band_lo), int(band_shift),
-                                                 _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
-        return {n: out[i] for i, n in enumerate(order)}
+        mask, order = self._mask(names)
+        n_tiles, count = self._tiles(tile0, n_tiles)
+        out = np.zeros((len(order), count, HIST_BINS), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_histogram(self.handle, mask, int(tile0), n_tiles, int(band_lo), int(band_shift),
+                                                 _host_ptr(out), _stream_arg(stream)))
+        return dict(zip(order, out))
 
     def crosstab(self, pairs, other=None, tile0=0, n_tiles=None, stream=None):
         """dswx_batch_crosstab: uint64 [n_pairs, n_tiles, 256], for every pair (name_a, name_b, spec) plane name_a of this
@@ -1667,16 +1661,11 @@ class DeviceBatch:
         pairs = list(pairs)
         arr = (CrosstabPair * max(len(pairs), 1))()
         for k, (name_a, name_b, spec) in enumerate(pairs):
-            for n in (name_a, name_b):
-                if n not in PLANE_INDEX:
-                    raise ValueError(f'unknown plane {n!r}')
-            arr[k].plane_a, arr[k].plane_b, arr[k].spec = PLANE_INDEX[name_a], PLANE_INDEX[name_b], CrosstabSpec.of(spec)
-        if n_tiles is None:
-            n_tiles = BATCH_ALL_TILES
-        count = self.n_tiles - tile0 if n_tiles == BATCH_ALL_TILES else n_tiles
-        out = np.zeros((len(pairs), max(int(count), 0), CROSSTAB_CELLS), dtype=np.uint64)
-        _check(self.ctx.lib.dswx_batch_crosstab(self.handle, other.handle, arr, len(pairs), int(tile0), int(n_tiles),
-                                                _host_ptr(out), ctypes.c_void_p(stream) if stream else None))
+            arr[k].plane_a, arr[k].plane_b, arr[k].spec = _plane_index(name_a), _plane_index(name_b), CrosstabSpec.of(spec)
+        n_tiles, count = self._tiles(tile0, n_tiles)
+        out = np.zeros((len(pairs), count, CROSSTAB_CELLS), dtype=np.uint64)
+        _check(self.ctx.lib.dswx_batch_crosstab(self.handle, other.handle, arr, len(pairs), int(tile0), n_tiles,
+                                                _host_ptr(out), _stream_arg(stream)))
         return out
 
     def stack(self, name, spec, tile0=0, n_tiles=None, want=('count', 'last', 'last_index', 'share'), stream=None):
@@ -1685,20 +1674,14 @@ class DeviceBatch:
         DeviceBuffer} for the outputs named in `want`: 'count' uint16 [n_cats][H*W], 'last' uint8 [H*W], 'last_index' uint16
         [H*W], 'share' uint8 [H*W] -- device planes owned by the caller.  proteus_amd.stack.stack_tiles of the downloaded
         tiles gives the same planes."""
-        if name not in PLANE_INDEX:
-            raise ValueError(f'unknown plane {name!r}')
+        plane = _plane_index(name)
         n = max(self.n_pixels, 1)
-        res = _stack_planes(want, spec, (n,), lambda shp, dt: self.ctx.malloc(int(np.prod(shp)) * np.dtype(dt).itemsize))
+        res = _malloc_planes(self.ctx, _stack_planes(want, spec, (n,), lambda shp, dt: (shp, dt)))
         out = StackOut.of(count=[res['count'].ptr + 2 * n * k for k in range(spec.n_cats)] if 'count' in res else (),
                           **{k: res[k].ptr for k in ('last', 'last_index', 'share') if k in res})
-        try:
-            _check(self.ctx.lib.dswx_batch_stack(self.handle, PLANE_INDEX[name], ctypes.byref(StackSpec.of(spec)), int(tile0),
-                                                 int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
-                                                 ctypes.c_void_p(stream) if stream else None))
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_stack(self.handle, plane, ctypes.byref(StackSpec.of(spec)), int(tile0),
+                                                 self._tiles(tile0, n_tiles)[0], ctypes.byref(out), _stream_arg(stream)))
         return res
 
     def grid(self, name, spec, tile0=0, n_tiles=None, want=('count', 'share', 'coverage', 'major'), stream=None):
@@ -1707,25 +1690,17 @@ class DeviceBatch:
         DeviceBuffer} for the outputs named in `want`: 'count' uint32 [n_cats][n_tiles][GH*GW], 'share', 'coverage' and
         'major' uint8 [n_tiles][GH*GW] -- device planes owned by the caller.  proteus_amd.grid.grid_tiles of the downloaded
         tiles gives the same planes."""
-        if name not in PLANE_INDEX:
-            raise ValueError(f'unknown plane {name!r}')
+        plane = _plane_index(name)
         from .grid import grid_shape
-        if n_tiles == BATCH_ALL_TILES:
-            n_tiles = None
-        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
         gh, gw = grid_shape(self.height, self.width, spec)
         n = max(nt * gh * gw, 1)
-        res = _grid_planes(want, spec, (n,), lambda shp, dt: self.ctx.malloc(int(np.prod(shp)) * np.dtype(dt).itemsize))
+        res = _malloc_planes(self.ctx, _grid_planes(want, spec, (n,), lambda shp, dt: (shp, dt)))
         out = GridOut.of(count=[res['count'].ptr + 4 * n * k for k in range(spec.n_cats)] if 'count' in res else (),
                          **{k: res[k].ptr for k in ('share', 'coverage', 'major') if k in res})
-        try:
-            _check(self.ctx.lib.dswx_batch_grid(self.handle, PLANE_INDEX[name], ctypes.byref(GridSpec.of(spec)), int(tile0),
-                                                int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
-                                                ctypes.c_void_p(stream) if stream else None))
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_grid(self.handle, plane, ctypes.byref(GridSpec.of(spec)), int(tile0), n_tiles,
+                                                ctypes.byref(out), _stream_arg(stream)))
         return res
 
     def label(self, name, spec, tile0=0, n_tiles=None, want=('label', 'size', 'sieved', 'summary'), stream=None):
@@ -1734,23 +1709,14 @@ class DeviceBatch:
         outputs named in `want` and the ones they need ('label' always, 'size' with 'sieved' or 'summary'): 'label' and
         'size' uint32 [n_tiles][H*W], 'sieved' uint8 [n_tiles][H*W], 'summary' uint64 [n_tiles][40] -- device planes owned by
         the caller.  proteus_amd.label.label_tiles of the downloaded tiles gives the same planes."""
-        if name not in PLANE_INDEX:
-            raise ValueError(f'unknown plane {name!r}')
-        if n_tiles == BATCH_ALL_TILES:
-            n_tiles = None
-        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
-        px = self.height * self.width
-        res = {k: self.ctx.malloc(max(nt * (LABEL_SUMMARY_WORDS if k == 'summary' else px), 1) * np.dtype(LABEL_DTYPES[k]).itemsize)
-               for k in _label_wanted(want)}
+        plane = _plane_index(name)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
+        res = _malloc_planes(self.ctx, {k: ((nt, LABEL_SUMMARY_WORDS if k == 'summary' else self.n_pixels), LABEL_DTYPES[k])
+                                        for k in _label_wanted(want)})
         out = LabelOut.of(**{k: b.ptr for k, b in res.items()})
-        try:
-            _check(self.ctx.lib.dswx_batch_label(self.handle, PLANE_INDEX[name], ctypes.byref(LabelSpec.of(spec)), int(tile0),
-                                                 int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
-                                                 ctypes.c_void_p(stream) if stream else None))
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_label(self.handle, plane, ctypes.byref(LabelSpec.of(spec)), int(tile0), n_tiles,
+                                                 ctypes.byref(out), _stream_arg(stream)))
         return res
 
     def distance(self, name, spec, tile0=0, n_tiles=None, want=('dist2', 'nearest', 'summary'), stream=None):
@@ -1759,23 +1725,14 @@ class DeviceBatch:
         Returns {output: DeviceBuffer} for the outputs named in `want` and 'dist2' always: 'dist2' and 'nearest' uint32
         [n_tiles][H*W], 'within' uint8 [n_tiles][H*W] (needs spec.max_radius > 0), 'summary' uint64 [n_tiles][40] -- device
         planes owned by the caller.  proteus_amd.distance.distance_tiles of the downloaded tiles gives the same planes."""
-        if name not in PLANE_INDEX:
-            raise ValueError(f'unknown plane {name!r}')
-        if n_tiles == BATCH_ALL_TILES:
-            n_tiles = None
-        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
-        px = self.height * self.width
-        res = {k: self.ctx.malloc(max(nt * (DISTANCE_SUMMARY_WORDS if k == 'summary' else px), 1) * np.dtype(DISTANCE_DTYPES[k]).itemsize)
-               for k in _distance_wanted(want, spec)}
+        plane = _plane_index(name)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
+        res = _malloc_planes(self.ctx, {k: ((nt, DISTANCE_SUMMARY_WORDS if k == 'summary' else self.n_pixels), DISTANCE_DTYPES[k])
+                                        for k in _distance_wanted(want, spec)})
         out = DistanceOut.of(**{k: b.ptr for k, b in res.items()})
-        try:
-            _check(self.ctx.lib.dswx_batch_distance(self.handle, PLANE_INDEX[name], ctypes.byref(DistanceSpec.of(spec)), int(tile0),
-                                                    int(BATCH_ALL_TILES if n_tiles is None else n_tiles), ctypes.byref(out),
-                                                    ctypes.c_void_p(stream) if stream else None))
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_distance(self.handle, plane, ctypes.byref(DistanceSpec.of(spec)), int(tile0), n_tiles,
+                                                    ctypes.byref(out), _stream_arg(stream)))
         return res
 
     def body_table(self, value_name, spec, label, tile0=0, n_tiles=None, want=('dense', 'rows', 'head'), stream=None):
@@ -1786,26 +1743,15 @@ class DeviceBatch:
         named in `want` and 'dense' always: 'dense' uint32 [n_tiles][H*W], 'rows' uint32 [n_tiles][max_rows][16] (only with
         max_rows > 0), 'head' uint64 [n_tiles][8] -- device planes owned by the caller.  proteus_amd.bodies.body_table of
         the downloaded planes gives the same."""
-        if value_name is not None and value_name not in PLANE_INDEX:
-            raise ValueError(f'unknown plane {value_name!r}')
-        if n_tiles == BATCH_ALL_TILES:
-            n_tiles = None
-        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
-        res = {}
-        for k in _body_wanted(want, spec):
-            shape = _body_shape(k, nt, self.height, self.width, spec)
-            res[k] = self.ctx.malloc(max(int(np.prod(shape, dtype=np.int64)), 1) * np.dtype(BODY_DTYPES[k]).itemsize)
+        plane = -1 if value_name is None else _plane_index(value_name)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
+        res = _malloc_planes(self.ctx, {k: (_body_shape(k, nt, self.height, self.width, spec), BODY_DTYPES[k])
+                                        for k in _body_wanted(want, spec)})
         out = BodyOut.of(**{k: b.ptr for k, b in res.items()})
-        try:
-            _check(self.ctx.lib.dswx_batch_body_table(self.handle, -1 if value_name is None else PLANE_INDEX[value_name],
-                                                      ctypes.byref(BodySpec.of(spec)), int(tile0),
-                                                      int(BATCH_ALL_TILES if n_tiles is None else n_tiles),
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_body_table(self.handle, plane, ctypes.byref(BodySpec.of(spec)), int(tile0), n_tiles,
                                                       ctypes.c_void_p(getattr(label, 'ptr', label)), ctypes.byref(out),
-                                                      ctypes.c_void_p(stream) if stream else None))
-        except DswxError:
-            for buf in res.values():
-                buf.free()
-            raise
+                                                      _stream_arg(stream)))
         return res
 
     def outline(self, name, label_spec, spec, tile0=0, n_tiles=None, stream=None):
@@ -1815,16 +1761,9 @@ class DeviceBatch:
         [n_tiles][max_edges], 'rings' uint32 [n_tiles][max_rings][8] (only with spec.max_rings > 0), 'head' uint64
         [n_tiles][8] and 'label' uint32 [n_tiles][H*W] -- device planes owned by the caller.  (The library has no
         dswx_batch_outline: the input of the outline is the caller's label plane, not a plane of the batch.)"""
-        if n_tiles == BATCH_ALL_TILES:
-            n_tiles = None
-        nt = max(self.n_tiles - tile0, 0) if n_tiles is None else max(n_tiles, 0)
         res = self.label(name, label_spec, tile0, n_tiles, want=('label',), stream=stream)
-        try:
-            res.update(self.ctx.outline(res['label'], spec, nt, self.height, self.width, stream=stream))
-        except (DswxError, ValueError):
-            for buf in res.values():
-                buf.free()
-            raise
+        with _owned(res, (DswxError, ValueError)):
+            res.update(self.ctx.outline(res['label'], spec, self._tiles(tile0, n_tiles)[1], self.height, self.width, stream=stream))
         return res
 
     def read_tile(self, name, tile):

@@ -24,6 +24,7 @@
 #include <utility>
 #include <vector>
 
+#include "dswx_batch_select.h"
 #include "dswx_host.h"
 #include "dswx_vmm.h"
 
@@ -95,6 +96,39 @@ static void bind_structs(const dswx_batch* b, dswx_planes_in_t* in, dswx_planes_
     if (out) memset(out, 0, sizeof *out);
     for (const dswx_plane_desc& d : DSWX_PLANES)
         if (d.batch >= 0) dswx_plane_set(d, in, out, b->ptr[d.batch]);
+}
+
+// ---- The pieces of the entries that work on resident planes (dswx_batch_checksum ... dswx_batch_distance below); the rules
+// themselves are in dswx_batch_select.h.
+static dswx_batch_view view_of(const dswx_batch* b) {
+    return {b->geom.n_tiles, b->geom.height, b->geom.width, b->geom.tile_stride, b->device, b->ptr};
+}
+
+// ONE uint8 plane of a batch and a tile range of it, for the entries that take a plane index: the batch, the plane
+// (dswx_select_u8_plane), the range -> the view, the resolved n_tiles and tile `tile0` of the plane.
+static int select_u8(const dswx_batch* b, int plane, int lowest, const char* no_counters, const char* what, int64_t tile0, int64_t* n_tiles,
+                     dswx_batch_view* v, const uint8_t** base) {
+    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    *v = view_of(b);
+    if (int rc = dswx_select_u8_plane(*v, plane, lowest, no_counters, what, tile0, base)) return rc;
+    return dswx_select_tiles({v}, tile0, n_tiles, "the batch");
+}
+
+// The tail of the entries that hand their result to the host: `bytes` of device memory of this call's own -- no scratch of the
+// context, nothing to order against its other launches --, launch(dev, stream) fills them, they are copied to `out`, and the
+// stream is waited for.
+template <typename T, typename Launch>
+static int read_back(dswx_ctx* ctx, void* stream, size_t bytes, T* out, const char* entry, const char* what, Launch launch) {
+    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
+    T* dev = nullptr;
+    HIP_TRY(scratch.take(&dev, bytes));
+    if (int rc = launch(dev, scratch.s)) return rc;
+    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
+    if (e == hipSuccess) e = scratch.sync();
+    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "%s: reading the %s failed: %s", entry, what, hipGetErrorString(e));
+    return DSWX_OK;
 }
 
 extern "C" {
@@ -305,36 +339,22 @@ int dswx_batch_synth(dswx_batch_t* b, uint64_t seed, int64_t tile0, void* stream
 // this call's own -- no scratch of the context, nothing to order against its other launches.
 int dswx_batch_checksum(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, uint64_t* out, void* stream) {
     if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
+    if (int rc = dswx_select_mask(plane_mask, nullptr)) return rc;
+    const dswx_batch_view v = view_of(b);
+    if (int rc = dswx_select_tiles({&v}, tile0, &n_tiles, "the batch")) return rc;
     dswx_checksum_plane planes[DSWX_BATCH_MAX_PLANES];
     int n_planes = 0;
-    const uint64_t px = (uint64_t)b->geom.height * (uint64_t)b->geom.width, stride = (uint64_t)b->geom.tile_stride;
-    for (int k = 0; k < DSWX_BATCH_MAX_PLANES; ++k) {
-        if (!((plane_mask >> k) & 1u)) continue;
-        const bool counters = k == DSWX_PLANE_COUNTERS;
-        if (!b->ptr[k])
-            return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", k, counters ? "counters" : DSWX_PLANES[k].name);
-        const uint64_t eb = counters ? sizeof(int64_t) : DSWX_PLANES[k].bytes;
-        const uint64_t n = counters ? DSWX_N_COUNTERS : px, st = counters ? DSWX_N_COUNTERS : stride;
-        planes[n_planes++] = {(const char*)b->ptr[k] + (uint64_t)tile0 * st * eb, n * eb, st * eb};
-    }
+    const uint64_t px = (uint64_t)v.height * (uint64_t)v.width, stride = (uint64_t)v.tile_stride;
+    if (int rc = dswx_select_walk(plane_mask, v, nullptr, [&](int k) {
+            const bool counters = k == DSWX_PLANE_COUNTERS;
+            const uint64_t eb = counters ? sizeof(int64_t) : DSWX_PLANES[k].bytes;
+            const uint64_t n = counters ? DSWX_N_COUNTERS : px, st = counters ? DSWX_N_COUNTERS : stride;
+            planes[n_planes++] = {dswx_select_base(v, k, tile0), n * eb, st * eb};
+        }))
+        return rc;
     if (n_planes == 0 || n_tiles == 0) return DSWX_OK;
-    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
-    dswx_ctx* ctx = b->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n_planes * (size_t)n_tiles * sizeof(uint64_t);
-    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
-    uint64_t* dev = nullptr;
-    HIP_TRY(scratch.take(&dev, bytes));
-    if (int rc = dswx_checksum_launch(ctx, planes, n_planes, n_tiles, dev, scratch.s)) return rc;
-    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
-    if (e == hipSuccess) e = scratch.sync();
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_checksum: reading the checksums failed: %s", hipGetErrorString(e));
-    return DSWX_OK;
+    return read_back(b->ctx, stream, (size_t)n_planes * (size_t)n_tiles * sizeof(uint64_t), out, "dswx_batch_checksum", "checksums",
+                     [&](uint64_t* dev, hipStream_t s) { return dswx_checksum_launch(b->ctx, planes, n_planes, n_tiles, dev, s); });
 }
 
 // The selected planes of two resident batches compared pair by pair (dswx_compare.hip), one launch; like the checksums the
@@ -342,45 +362,26 @@ int dswx_batch_checksum(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int
 int dswx_batch_compare(dswx_batch_t* a, dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, double atol,
                        double rtol, int32_t equal_nan, dswx_compare_t* out, void* stream) {
     if (!a || !b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
-    if ((plane_mask >> DSWX_PLANE_COUNTERS) & 1u)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not compared here (24 bytes per tile): compare their checksums instead "
-                         "(dswx_batch_checksum with DSWX_PLANE_COUNTERS)");
-    if (a->device != b->device) return dswx_fail(DSWX_ERR_ARG, "the batches are on different devices (%d and %d)", a->device, b->device);
-    if (a->geom.height != b->geom.height || a->geom.width != b->geom.width)
-        return dswx_fail(DSWX_ERR_ARG, "the batches differ in tile size: %lld x %lld against %lld x %lld", (long long)a->geom.height,
-                         (long long)a->geom.width, (long long)b->geom.height, (long long)b->geom.width);
+    if (int rc = dswx_select_mask(plane_mask, "the counters are not compared here (24 bytes per tile): compare their checksums instead "
+                                              "(dswx_batch_checksum with DSWX_PLANE_COUNTERS)"))
+        return rc;
+    const dswx_batch_view va = view_of(a), vb = view_of(b);
+    if (int rc = dswx_select_compatible(va, vb)) return rc;
     if (int rc = dswx_compare_check_tol(atol, rtol)) return rc;
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= a->geom.n_tiles) n_tiles = a->geom.n_tiles - tile0;
-    for (const dswx_batch* x : {a, b})
-        if (tile0 < 0 || n_tiles < 0 || tile0 > x->geom.n_tiles || n_tiles > x->geom.n_tiles - tile0)
-            return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside a batch (%lld resident)", (long long)tile0, (long long)n_tiles,
-                             (long long)x->geom.n_tiles);
+    if (int rc = dswx_select_tiles({&va, &vb}, tile0, &n_tiles, "a batch")) return rc;
     dswx_compare_pair pairs[DSWX_BATCH_MAX_PLANES];
     int n_pairs = 0;
-    const uint64_t px = (uint64_t)a->geom.height * (uint64_t)a->geom.width;
-    for (int k = 0; k < DSWX_PLANE_COUNTERS; ++k) {
-        if (!((plane_mask >> k) & 1u)) continue;
-        const dswx_plane_desc& d = DSWX_PLANES[k];
-        if (!a->ptr[k] || !b->ptr[k])
-            return dswx_fail(DSWX_ERR_ARG, "batch %s has no plane %d (%s)", !a->ptr[k] ? (!b->ptr[k] ? "a (nor b)" : "a") : "b", k, d.name);
-        const uint64_t sa = (uint64_t)a->geom.tile_stride, sb = (uint64_t)b->geom.tile_stride;
-        pairs[n_pairs++] = {(const char*)a->ptr[k] + (uint64_t)tile0 * sa * d.bytes, (const char*)b->ptr[k] + (uint64_t)tile0 * sb * d.bytes,
-                            d.kind, px, sa, sb};
-    }
+    const uint64_t px = (uint64_t)va.height * (uint64_t)va.width;
+    if (int rc = dswx_select_walk(plane_mask, va, &vb, [&](int k) {
+            pairs[n_pairs++] = {dswx_select_base(va, k, tile0), dswx_select_base(vb, k, tile0), DSWX_PLANES[k].kind, px,
+                                (uint64_t)va.tile_stride, (uint64_t)vb.tile_stride};
+        }))
+        return rc;
     if (n_pairs == 0 || n_tiles == 0) return DSWX_OK;
-    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
-    dswx_ctx* ctx = a->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n_pairs * (size_t)n_tiles * sizeof(dswx_compare_t);
-    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
-    dswx_compare_t* dev = nullptr;
-    HIP_TRY(scratch.take(&dev, bytes));
-    if (int rc = dswx_compare_launch(ctx, pairs, n_pairs, n_tiles, atol, rtol, equal_nan, dev, scratch.s)) return rc;
-    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
-    if (e == hipSuccess) e = scratch.sync();
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_compare: reading the records failed: %s", hipGetErrorString(e));
-    return DSWX_OK;
+    return read_back(a->ctx, stream, (size_t)n_pairs * (size_t)n_tiles * sizeof(dswx_compare_t), out, "dswx_batch_compare", "records",
+                     [&](dswx_compare_t* dev, hipStream_t s) {
+                         return dswx_compare_launch(a->ctx, pairs, n_pairs, n_tiles, atol, rtol, equal_nan, dev, s);
+                     });
 }
 
 // Per-tile histograms of the selected planes (dswx_histogram.hip), one launch; like the checksums the device words live in an
@@ -389,39 +390,24 @@ int dswx_batch_compare(dswx_batch_t* a, dswx_batch_t* b, uint32_t plane_mask, in
 int dswx_batch_histogram(dswx_batch_t* b, uint32_t plane_mask, int64_t tile0, int64_t n_tiles, int32_t band_lo, int32_t band_shift,
                          uint64_t* out, void* stream) {
     if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane_mask >> DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane_mask 0x%x names planes past %d", plane_mask, DSWX_BATCH_MAX_PLANES - 1);
-    if ((plane_mask >> DSWX_PLANE_COUNTERS) & 1u)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not histogrammed (three int64 per tile): read them (dswx_batch_planes)");
+    if (int rc = dswx_select_mask(plane_mask, "the counters are not histogrammed (three int64 per tile): read them (dswx_batch_planes)"))
+        return rc;
     if (int rc = dswx_histogram_check_kind(DSWX_HIST_I16, band_shift)) return rc;
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
+    const dswx_batch_view v = view_of(b);
+    if (int rc = dswx_select_tiles({&v}, tile0, &n_tiles, "the batch")) return rc;
     dswx_histogram_plane planes[DSWX_BATCH_MAX_PLANES];
     int n_planes = 0;
-    const uint64_t px = (uint64_t)b->geom.height * (uint64_t)b->geom.width, stride = (uint64_t)b->geom.tile_stride;
-    for (int k = 0; k < DSWX_PLANE_COUNTERS; ++k) {
-        if (!((plane_mask >> k) & 1u)) continue;
-        const dswx_plane_desc& d = DSWX_PLANES[k];
-        if (!b->ptr[k]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", k, d.name);
-        const int kind = k == DSWX_PLANE_DIAG ? DSWX_HIST_DIAG : d.kind == DSWX_CMP_I16 ? DSWX_HIST_I16 : DSWX_HIST_U8;
-        static_assert(DSWX_PLANES[DSWX_PLANE_DIAG].kind == DSWX_CMP_U16, "DIAG is a uint16 plane, every plane is 8 or 16 bits wide");
-        planes[n_planes++] = {(const char*)b->ptr[k] + (uint64_t)tile0 * stride * d.bytes, kind, kind == DSWX_HIST_I16 ? band_lo : 0,
-                              kind == DSWX_HIST_I16 ? band_shift : 0, px, stride};
-    }
+    const uint64_t px = (uint64_t)v.height * (uint64_t)v.width;
+    if (int rc = dswx_select_walk(plane_mask, v, nullptr, [&](int k) {
+            const int kind = k == DSWX_PLANE_DIAG ? DSWX_HIST_DIAG : DSWX_PLANES[k].kind == DSWX_CMP_I16 ? DSWX_HIST_I16 : DSWX_HIST_U8;
+            static_assert(DSWX_PLANES[DSWX_PLANE_DIAG].kind == DSWX_CMP_U16, "DIAG is a uint16 plane, every plane is 8 or 16 bits wide");
+            planes[n_planes++] = {dswx_select_base(v, k, tile0), kind, kind == DSWX_HIST_I16 ? band_lo : 0,
+                                  kind == DSWX_HIST_I16 ? band_shift : 0, px, (uint64_t)v.tile_stride};
+        }))
+        return rc;
     if (n_planes == 0 || n_tiles == 0) return DSWX_OK;
-    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
-    dswx_ctx* ctx = b->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n_planes * (size_t)n_tiles * DSWX_HIST_BINS * sizeof(uint64_t);
-    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
-    uint64_t* dev = nullptr;
-    HIP_TRY(scratch.take(&dev, bytes));
-    if (int rc = dswx_histogram_launch(ctx, planes, n_planes, n_tiles, dev, scratch.s)) return rc;
-    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
-    if (e == hipSuccess) e = scratch.sync();
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_histogram: reading the histograms failed: %s", hipGetErrorString(e));
-    return DSWX_OK;
+    return read_back(b->ctx, stream, (size_t)n_planes * (size_t)n_tiles * DSWX_HIST_BINS * sizeof(uint64_t), out, "dswx_batch_histogram",
+                     "histograms", [&](uint64_t* dev, hipStream_t s) { return dswx_histogram_launch(b->ctx, planes, n_planes, n_tiles, dev, s); });
 }
 
 // Plane pairs of two resident batches (or of one) cross-tabulated (dswx_crosstab.hip), one launch; like the checksums the
@@ -438,66 +424,40 @@ int dswx_batch_crosstab(dswx_batch_t* a, dswx_batch_t* b, const dswx_crosstab_pa
             if (p == DSWX_PLANE_COUNTERS)
                 return dswx_fail(DSWX_ERR_ARG, "the counters are not cross-tabulated (three int64 per tile): read them (dswx_batch_planes)");
         }
-    if (a->device != b->device) return dswx_fail(DSWX_ERR_ARG, "the batches are on different devices (%d and %d)", a->device, b->device);
-    if (a->geom.height != b->geom.height || a->geom.width != b->geom.width)
-        return dswx_fail(DSWX_ERR_ARG, "the batches differ in tile size: %lld x %lld against %lld x %lld", (long long)a->geom.height,
-                         (long long)a->geom.width, (long long)b->geom.height, (long long)b->geom.width);
+    const dswx_batch_view va = view_of(a), vb = view_of(b);
+    if (int rc = dswx_select_compatible(va, vb)) return rc;
     for (int k = 0; k < n_pairs; ++k)
         if (int rc = dswx_crosstab_check_spec(&pairs[k].spec)) return rc;
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= a->geom.n_tiles) n_tiles = a->geom.n_tiles - tile0;
-    for (const dswx_batch* x : {a, b})
-        if (tile0 < 0 || n_tiles < 0 || tile0 > x->geom.n_tiles || n_tiles > x->geom.n_tiles - tile0)
-            return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside a batch (%lld resident)", (long long)tile0, (long long)n_tiles,
-                             (long long)x->geom.n_tiles);
+    if (int rc = dswx_select_tiles({&va, &vb}, tile0, &n_tiles, "a batch")) return rc;
     dswx_crosstab_item items[DSWX_CROSSTAB_MAX_PAIRS];
-    const uint64_t px = (uint64_t)a->geom.height * (uint64_t)a->geom.width;
-    const uint64_t sa = (uint64_t)a->geom.tile_stride, sb = (uint64_t)b->geom.tile_stride;
+    const uint64_t px = (uint64_t)va.height * (uint64_t)va.width;
     for (int k = 0; k < n_pairs; ++k) {
         const int pa = pairs[k].plane_a, pb = pairs[k].plane_b, kind = pairs[k].spec.a_kind;
         const dswx_plane_desc& da = DSWX_PLANES[pa];
         const dswx_plane_desc& db = DSWX_PLANES[pb];
-        if (!a->ptr[pa]) return dswx_fail(DSWX_ERR_ARG, "batch a has no plane %d (%s)", pa, da.name);
-        if (!b->ptr[pb]) return dswx_fail(DSWX_ERR_ARG, "batch b has no plane %d (%s)", pb, db.name);
+        if (!va.ptr[pa]) return dswx_fail(DSWX_ERR_ARG, "batch a has no plane %d (%s)", pa, da.name);
+        if (!vb.ptr[pb]) return dswx_fail(DSWX_ERR_ARG, "batch b has no plane %d (%s)", pb, db.name);
         const bool fits = pa == DSWX_PLANE_DIAG ? kind == DSWX_HIST_DIAG || kind == DSWX_HIST_U16
                           : da.kind == DSWX_CMP_I16 ? kind == DSWX_HIST_I16 : kind == DSWX_HIST_U8;
         if (!fits) return dswx_fail(DSWX_ERR_ARG, "pair %d: a_kind %d does not bin plane %d (%s), %d bytes per pixel", k, kind, pa, da.name, da.bytes);
         if (db.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "pair %d: plane b must be a uint8 plane, plane %d (%s) has %d bytes per pixel", k, pb, db.name, db.bytes);
-        items[k] = {(const char*)a->ptr[pa] + (uint64_t)tile0 * sa * da.bytes, (const char*)b->ptr[pb] + (uint64_t)tile0 * sb, &pairs[k].spec,
-                    px, sa, sb};
+        items[k] = {dswx_select_base(va, pa, tile0), dswx_select_base(vb, pb, tile0), &pairs[k].spec, px, (uint64_t)va.tile_stride,
+                    (uint64_t)vb.tile_stride};
     }
     if (n_pairs == 0 || n_tiles == 0) return DSWX_OK;
-    if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
-    dswx_ctx* ctx = a->ctx;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const size_t bytes = (size_t)n_pairs * (size_t)n_tiles * DSWX_CROSSTAB_CELLS * sizeof(uint64_t);
-    dswx_call_scratch scratch(dswx_stream_of(ctx, stream));
-    uint64_t* dev = nullptr;
-    HIP_TRY(scratch.take(&dev, bytes));
-    if (int rc = dswx_crosstab_launch(ctx, items, n_pairs, n_tiles, dev, scratch.s)) return rc;
-    hipError_t e = hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, scratch.s);
-    if (e == hipSuccess) e = scratch.sync();
-    if (e != hipSuccess) return dswx_fail(DSWX_ERR_HIP, "dswx_batch_crosstab: reading the tables failed: %s", hipGetErrorString(e));
-    return DSWX_OK;
+    return read_back(a->ctx, stream, (size_t)n_pairs * (size_t)n_tiles * DSWX_CROSSTAB_CELLS * sizeof(uint64_t), out, "dswx_batch_crosstab",
+                     "tables", [&](uint64_t* dev, hipStream_t s) { return dswx_crosstab_launch(a->ctx, items, n_pairs, n_tiles, dev, s); });
 }
 
 // The tiles of ONE uint8 plane of a resident batch composited per pixel (dswx_stack.hip), one launch, asynchronous: the
 // outputs are the caller's device planes, so nothing is allocated, copied or waited for here.
 int dswx_batch_stack(dswx_batch_t* b, int32_t plane, const dswx_stack_spec_t* spec, int64_t tile0, int64_t n_tiles,
                      const dswx_stack_out_t* out, void* stream) {
-    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
-    if (plane == DSWX_PLANE_COUNTERS)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not stacked (three int64 per tile): read them (dswx_batch_planes)");
-    const dswx_plane_desc& d = DSWX_PLANES[plane];
-    if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "a stack is a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
-    if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
-    const int64_t px = b->geom.height * b->geom.width;
-    int64_t stride = b->geom.tile_stride;
-    const uint8_t* base = (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride;
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not stacked", "a stack is a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    const int64_t px = v.height * v.width;
+    int64_t stride = v.tile_stride;
     if (int rc = dswx_stack_check(base, spec, n_tiles, px, &stride, out, true)) return rc;
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
@@ -508,46 +468,28 @@ int dswx_batch_stack(dswx_batch_t* b, int32_t plane, const dswx_stack_spec_t* sp
 // are the caller's device planes, so nothing is allocated, copied or waited for here.
 int dswx_batch_grid(dswx_batch_t* b, int32_t plane, const dswx_grid_spec_t* spec, int64_t tile0, int64_t n_tiles,
                     const dswx_grid_out_t* out, void* stream) {
-    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
-    if (plane == DSWX_PLANE_COUNTERS)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not gridded (three int64 per tile): read them (dswx_batch_planes)");
-    const dswx_plane_desc& d = DSWX_PLANES[plane];
-    if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "a grid is made of a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
-    if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
-    int64_t stride = b->geom.tile_stride;
-    const uint8_t* base = (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride;
-    if (int rc = dswx_grid_check(base, spec, n_tiles, b->geom.height, b->geom.width, &stride, out, true)) return rc;
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not gridded", "a grid is made of a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    int64_t stride = v.tile_stride;
+    if (int rc = dswx_grid_check(base, spec, n_tiles, v.height, v.width, &stride, out, true)) return rc;
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_grid_launch(ctx, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_grid_launch(ctx, base, spec, n_tiles, v.height, v.width, stride, out, dswx_stream_of(ctx, stream));
 }
 
 // The connected bodies of ONE uint8 plane of a resident batch (dswx_label.hip), asynchronous: the outputs are the caller's
 // device planes, so nothing is allocated, copied or waited for here.
 int dswx_batch_label(dswx_batch_t* b, int32_t plane, const dswx_label_spec_t* spec, int64_t tile0, int64_t n_tiles,
                      const dswx_label_out_t* out, void* stream) {
-    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
-    if (plane == DSWX_PLANE_COUNTERS)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not labelled (three int64 per tile): read them (dswx_batch_planes)");
-    const dswx_plane_desc& d = DSWX_PLANES[plane];
-    if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "bodies are labelled in a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
-    if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
-    int64_t stride = b->geom.tile_stride;
-    const uint8_t* base = (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride;
-    if (int rc = dswx_label_check(base, spec, n_tiles, b->geom.height, b->geom.width, &stride, out, true)) return rc;
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not labelled", "bodies are labelled in a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    int64_t stride = v.tile_stride;
+    if (int rc = dswx_label_check(base, spec, n_tiles, v.height, v.width, &stride, out, true)) return rc;
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_label_launch(ctx, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_label_launch(ctx, base, spec, n_tiles, v.height, v.width, stride, out, dswx_stream_of(ctx, stream));
 }
 
 // The bodies of a label plane of the caller tabulated against ONE uint8 plane of a resident batch, or none
@@ -555,48 +497,29 @@ int dswx_batch_label(dswx_batch_t* b, int32_t plane, const dswx_label_spec_t* sp
 // allocated, copied or waited for here.
 int dswx_batch_body_table(dswx_batch_t* b, int32_t plane, const dswx_body_spec_t* spec, int64_t tile0, int64_t n_tiles,
                           const uint32_t* label, const dswx_body_out_t* out, void* stream) {
-    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane < -1 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not -1 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
-    if (plane == DSWX_PLANE_COUNTERS)
-        return dswx_fail(DSWX_ERR_ARG, "the counters are not tabulated (three int64 per tile): read them (dswx_batch_planes)");
-    if (plane >= 0) {
-        const dswx_plane_desc& d = DSWX_PLANES[plane];
-        if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "bodies are tabulated against a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
-        if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
-    }
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
-    int64_t stride = b->geom.tile_stride;
-    const uint8_t* base = plane >= 0 ? (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride : nullptr;
-    if (int rc = dswx_body_check(label, base, spec, n_tiles, b->geom.height, b->geom.width, &stride, out, true)) return rc;
+    dswx_batch_view v;
+    const uint8_t* base;          // NULL for plane -1: no value plane
+    if (int rc = select_u8(b, plane, -1, "the counters are not tabulated", "bodies are tabulated against a uint8 plane", tile0, &n_tiles, &v, &base))
+        return rc;
+    int64_t stride = v.tile_stride;
+    if (int rc = dswx_body_check(label, base, spec, n_tiles, v.height, v.width, &stride, out, true)) return rc;
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_body_launch(ctx, label, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_body_launch(ctx, label, base, spec, n_tiles, v.height, v.width, stride, out, dswx_stream_of(ctx, stream));
 }
 
 // The distance of every pixel to the nearest target in ONE uint8 plane of a resident batch (dswx_distance.hip), asynchronous:
 // the outputs are the caller's device planes, so nothing is allocated, copied or waited for here.
 int dswx_batch_distance(dswx_batch_t* b, int32_t plane, const dswx_distance_spec_t* spec, int64_t tile0, int64_t n_tiles,
                         const dswx_distance_out_t* out, void* stream) {
-    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
-    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
-    if (plane == DSWX_PLANE_COUNTERS)
-        return dswx_fail(DSWX_ERR_ARG, "the counters have no distances (three int64 per tile): read them (dswx_batch_planes)");
-    const dswx_plane_desc& d = DSWX_PLANES[plane];
-    if (d.bytes != 1) return dswx_fail(DSWX_ERR_ARG, "distances are measured in a uint8 plane, plane %d (%s) has %d bytes per pixel", plane, d.name, d.bytes);
-    if (!b->ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
-    if (n_tiles == DSWX_BATCH_ALL_TILES && tile0 >= 0 && tile0 <= b->geom.n_tiles) n_tiles = b->geom.n_tiles - tile0;
-    if (tile0 < 0 || n_tiles < 0 || tile0 > b->geom.n_tiles || n_tiles > b->geom.n_tiles - tile0)
-        return dswx_fail(DSWX_ERR_ARG, "tiles %lld .. +%lld outside the batch (%lld resident)", (long long)tile0,
-                         (long long)n_tiles, (long long)b->geom.n_tiles);
-    int64_t stride = b->geom.tile_stride;
-    const uint8_t* base = (const uint8_t*)b->ptr[plane] + (uint64_t)tile0 * (uint64_t)stride;
-    if (int rc = dswx_distance_check(base, spec, n_tiles, b->geom.height, b->geom.width, &stride, out, true)) return rc;
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters have no distances", "distances are measured in a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    int64_t stride = v.tile_stride;
+    if (int rc = dswx_distance_check(base, spec, n_tiles, v.height, v.width, &stride, out, true)) return rc;
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_distance_launch(ctx, base, spec, n_tiles, b->geom.height, b->geom.width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_distance_launch(ctx, base, spec, n_tiles, v.height, v.width, stride, out, dswx_stream_of(ctx, stream));
 }
 
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
