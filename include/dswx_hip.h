@@ -1168,6 +1168,105 @@ int dswx_outline_device(dswx_ctx_t* ctx, const uint32_t* ids, const dswx_outline
 int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                       const dswx_outline_out_t* out_host);
 
+/* ---- burn: polygon rings rasterised onto planes -- the opposite direction of the outline (additive to ABI v7)
+ * label, body table and outline go from a resident plane to vectors.  These entries go back: the edges of polygon rings
+ * become pixels, without a plane crossing PCIe -- a coastline, an area of interest or an edited lake polygon becomes a plane
+ * on the device, or is burnt straight into the OCEAN plane of a resident batch in front of dswx_batch_classify.  What the
+ * reference does with gdal.RasterizeLayer(burn_values=[1]) in _create_ocean_mask (dswx_hls.py:3464-3572).  A C caller tests
+ * for the entries with DSWX_HAS_BURN.  STILL REFUSED: reading .shp files, reprojecting from the SRS of a shapefile, and the
+ * metric Buffer(margin_m) of the VECTOR (the distance entry's `within` buffers the RASTER afterwards).
+ * UNPINNED: GDAL is not part of this project's environment, so GDAL's handling of a pixel centre that lies exactly on an edge
+ * is not pinned by any test.  The definition below is this project's own; it agrees with GDAL's documented default (a pixel
+ * is burnt when its CENTRE is inside) wherever no centre lies exactly on an edge.
+ * THE DEFINITION.  Coordinates are int32 in units of 1/256 pixel, x right and y down: pixel (c, r) has its centre at
+ * (256 c + 128, 256 r + 128).  A coordinate v is LEGAL iff |v| <= 2^30 (DSWX_BURN_MAX_COORD).  Rows do not wrap and tiles never
+ * see each other.
+ *   INPUT      `verts`: records of 16 bytes {int32 x, y; uint32 word; uint32 next}.  `tile_first`: int64 [n_tiles + 1]; tile t
+ *              owns the records tile_first[t] .. tile_first[t + 1] - 1 of `verts`: its count is tile_first[t + 1] -
+ *              tile_first[t], and ZERO when that is negative or tile_first[t] is: a decreasing table means that the affected
+ *              tiles have no records.  Record i of a tile (counted from the tile's first) is the directed edge from its
+ *              (x, y) to the (x, y) of record `next` of the same tile.  A closed ring is a cycle of `next`; the rasterisation
+ *              needs only the multiset of edges, so nothing checks that the cycles close.  ANY CONTENT OF A RECORD IS LEGAL: a
+ *              record is MALFORMED when its `next` is >= the count of its tile, or when one of the four coordinates of its
+ *              two endpoints is not legal.  A malformed record contributes nothing and is counted; `next` is compared with
+ *              the count before the record it names is read.
+ *   CROSSING   orient the edge so that y0 < y1; an edge with y0 == y1 contributes nothing.  The edge CROSSES row r iff
+ *              y0 <= 256 r + 128 < y1 and 0 <= r < height.  For such a row, with yc = 256 r + 128,
+ *                  col = max(0, ceil(((x1 - x0) * (yc - y0) + (x0 - 128) * (y1 - y0)) / (256 * (y1 - y0))))
+ *              in exact integer arithmetic: the first pixel of the row whose centre is at or to the right of the crossing
+ *              (with legal coordinates every intermediate stays below 2^63).  If col < width the crossing TOGGLES:
+ *              acc[r][col] ^= word; otherwise it is dropped.
+ *   RESULT     acc[r][c] is the XOR of all toggles of row r at columns <= c: the XOR of the words of all edges that cross row
+ *              r at or to the left of the centre of (c, r).  Rows are half-open at the bottom end of an edge, columns closed
+ *              on the left.  For one ring with word w, acc is w exactly on the pixels whose centre is inside by the even-odd
+ *              rule; if every polygon of a set has a bit of its own, acc != 0 is their union; and if every ring that
+ *              dswx_outline_* returns for an id plane gets its id as word, acc IS that id plane, whatever the plane holds and
+ *              with either connectivity.
+ *   acc        uint32 [n_tiles][height * width], dense.  REQUIRED: it is the working array;
+ *   mask       uint8 [n_tiles][mask_tile_stride] (0 = height * width): mask[p] = acc[p] != 0 ? burn : (src ? src[p] :
+ *              background); the bytes between height * width and the stride are not touched.  NULL = not wanted.  `src` is an
+ *              optional uint8 plane [n_tiles][src_tile_stride] (0 = height * width) and MAY BE `mask` ITSELF, with the same
+ *              stride: burn in place, several calls OR together.  Any other overlap is NOT CHECKED;
+ *   head       uint64 [n_tiles][DSWX_BURN_HEAD_WORDS]: word 0 the records of the tile; 1 the malformed ones; 2 the edges that
+ *              cross at least one row of the tile; 3 the toggles applied; 4 the crossings dropped at col >= width; 5 the
+ *              crossings whose column was negative before the clamp to 0 (applied or dropped, they count in 3 or 4 too); 6 the
+ *              pixels with acc != 0; 7 zero.  NULL = not wanted.
+ * height * width <= 2^30, as for the outline.  n_tiles == 0 writes nothing.  All of it is integer arithmetic: the result is
+ * deterministic and independent of the launch geometry and of the order in which atomics arrive (XOR and integer addition
+ * commute). */
+#define DSWX_HAS_BURN 1
+#define DSWX_BURN_HEAD_WORDS 8
+#define DSWX_BURN_MAX_COORD (1 << 30)
+typedef struct dswx_burn_vertex {
+    int32_t x, y;                      /* 1/256 pixel */
+    uint32_t word;                     /* what a crossing of the edge that starts here toggles */
+    uint32_t next;                     /* the record at which that edge ends, counted from the tile's first record */
+} dswx_burn_vertex_t;                  /* 16 bytes */
+typedef struct dswx_burn_spec {
+    int32_t burn;                      /* 0 .. 255: the byte of a pixel with acc != 0 in `mask` */
+    int32_t background;                /* 0 .. 255: the byte of every other pixel when there is no `src` */
+    int64_t mask_tile_stride;          /* elements between the tiles of `mask`; 0 = height * width */
+    int64_t src_tile_stride;           /* elements between the tiles of `src`; 0 = height * width */
+} dswx_burn_spec_t;                    /* 24 bytes */
+typedef struct dswx_burn_out {
+    uint32_t* acc;                     /* [n_tiles][height * width]; REQUIRED: the working array */
+    uint8_t*  mask;                    /* [n_tiles][mask_tile_stride]; NULL = not wanted */
+    uint64_t* head;                    /* [n_tiles][8]; NULL = not wanted */
+} dswx_burn_out_t;
+/* Records and table in DEVICE memory -> the wanted outputs of *out_device (device memory).  Asynchronous on `stream` (NULL =
+ * the context's stream): one hipMemsetAsync each of `acc` and `head` and two kernel launches -- every record computes its
+ * first crossing with one 64-bit division and steps it exactly down the rows (an edge of more than a few rows is shared out
+ * over the lanes of its wave), each crossing one atomic XOR on `acc`, the counts summed per workgroup before one set of
+ * 64-bit atomics; then an XOR prefix along every row of `acc` in place, which also writes `mask` and counts the pixels.  No
+ * synchronisation, no scratch of the context, no allocation, no working memory and nothing the caller has to zero in front: a
+ * second call on the same outputs gives the same bytes (with `src` == `mask` the second call burns into the first one's
+ * result, which leaves it as it is).  No workgroup ever waits for another.  `tile_first` is read ON THE DEVICE ONLY: its
+ * content is not validated on the host, the records it names must lie inside `verts` (NOT CHECKED), and a decreasing table
+ * gives the affected tiles zero records as stated above.  A NULL spec or out struct, `burn` or `background` outside 0 .. 255,
+ * a negative size, tile count or stride, a stride that is neither 0 nor at least height * width, height * width above 2^30,
+ * more than 2^32 tiles, NULL verts or tile_first with n_tiles > 0, a NULL acc with something to write, or `src` without
+ * `mask`: DSWX_ERR_ARG; verts off 16 bytes, acc off 4, or tile_first or head off 8: DSWX_ERR_ALIGN.  `mask` and `src` take
+ * any address.  (The arguments are checked before the context is, and a refused call writes nothing.) */
+int dswx_burn_device(dswx_ctx_t* ctx, const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec,
+                     int64_t n_tiles, int64_t height, int64_t width, const uint8_t* src, const dswx_burn_out_t* out_device,
+                     void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table: Fmask, the masks, every layer but DIAG;
+ * DSWX_PLANE_OCEAN is the natural target) of a resident batch is BOTH `mask` and `src`, at the batch's tile stride, for tiles
+ * tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last): the polygons are burnt into the plane in
+ * place, tile_first[0] belongs to tile0, and acc_device (required) and head_device (NULL = not wanted) are the caller's device
+ * memory with tile 0 = tile0.  THE FIRST dswx_batch_* ENTRY THAT WRITES A PLANE OF THE BATCH: every earlier one only reads
+ * them.  Asynchronous on `stream` (NULL = the stream of the batch's context) like dswx_burn_device.  The two strides of
+ * `spec` must be 0: DSWX_ERR_ARG otherwise.  A plane that is not uint8 (the bands, DIAG), a plane the batch does not have, or
+ * DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the plane.  Tile ranges: the rules of dswx_batch_compare. */
+int dswx_batch_burn(dswx_batch_t* batch, int32_t plane, const dswx_burn_vertex_t* verts_device, const int64_t* tile_first_device,
+                    const dswx_burn_spec_t* spec, uint32_t* acc_device, uint64_t* head_device, int64_t tile0, int64_t n_tiles,
+                    void* stream);
+/* The same definition on HOST buffers in plain scalar C++, one division per crossing: needs no device and no context.  The
+ * other half of a comparison, not a fallback of the two entries above.  The refusals of dswx_burn_device, except that every
+ * buffer may sit at any address. */
+int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles,
+                   int64_t height, int64_t width, const uint8_t* src, const dswx_burn_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1196,7 +1295,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -47,7 +47,8 @@ EXPORTED_SYMBOLS = (
     'dswx_label_device', 'dswx_batch_label', 'dswx_label_host',
     'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host',
     'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host',
-    'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host')
+    'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host',
+    'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -73,6 +74,11 @@ DISTANCE_NONE, DISTANCE_SUMMARY_WORDS, DISTANCE_MAX_WIDTH, DISTANCE_MAX_SIDE = 0
 DISTANCE_BAND_H, DISTANCE_COLS, DISTANCE_BLOCK_W, DISTANCE_NEAR = 64, 4, 64, 32
 HAS_OUTLINE = 1                   # DSWX_HAS_OUTLINE: additive to ABI v7
 OUTLINE_ROW_WORDS, OUTLINE_HEAD_WORDS = 8, 8
+HAS_BURN = 1                      # DSWX_HAS_BURN: additive to ABI v7
+BURN_HEAD_WORDS, BURN_MAX_COORD = 8, 1 << 30
+# csrc/dswx_burn_rule.h: the rows of an edge that its own thread finishes (a longer edge is shared out over the wave) and the
+# pixels of a row that a wave of the scan launch takes per step (tests build shapes around the seams)
+BURN_THREAD_ROWS, BURN_SCAN_STEP = 4, 256
 
 
 class DswxError(RuntimeError):
@@ -297,10 +303,30 @@ class OutlineOut(ctypes.Structure):
         return cls(chain or None, rings or None, head or None)
 
 
+class BurnSpec(ctypes.Structure):
+    """dswx_burn_spec_t; proteus_amd.burn.Spec is the Python form."""
+    _fields_ = [('burn', ctypes.c_int32), ('background', ctypes.c_int32), ('mask_tile_stride', ctypes.c_int64),
+                ('src_tile_stride', ctypes.c_int64)]
+
+    @classmethod
+    def of(cls, spec):
+        return cls(spec.burn, spec.background, spec.mask_tile_stride, spec.src_tile_stride)
+
+
+class BurnOut(ctypes.Structure):
+    """dswx_burn_out_t: addresses, 0 / None = not wanted."""
+    _fields_ = [('acc', ctypes.c_void_p), ('mask', ctypes.c_void_p), ('head', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, acc=None, mask=None, head=None):
+        return cls(acc or None, mask or None, head or None)
+
+
 # the struct mirrors of the analytic entries by their C names (the offset tests compile the header against them)
 ANALYTIC_STRUCTS = {'dswx_label_spec_t': LabelSpec, 'dswx_label_out_t': LabelOut, 'dswx_body_spec_t': BodySpec,
                     'dswx_body_out_t': BodyOut, 'dswx_distance_spec_t': DistanceSpec, 'dswx_distance_out_t': DistanceOut,
-                    'dswx_outline_spec_t': OutlineSpec, 'dswx_outline_out_t': OutlineOut}
+                    'dswx_outline_spec_t': OutlineSpec, 'dswx_outline_out_t': OutlineOut,
+                    'dswx_burn_spec_t': BurnSpec, 'dswx_burn_out_t': BurnOut}
 
 COG_MAX_LEVELS = 8
 
@@ -490,6 +516,9 @@ def load_library(path=None):
         'dswx_outline_work_bytes': (ctypes.c_int, [vp, i64, i64, i64, vp]),
         'dswx_outline_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, ctypes.c_uint64, vp]),
         'dswx_outline_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp]),
+        'dswx_burn_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
+        'dswx_batch_burn': (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp, vp, vp, i64, i64, vp]),
+        'dswx_burn_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -1178,6 +1207,50 @@ class Context:
                 work.free()
         return res
 
+    def burn_device(self, verts_ptr, tile_first_ptr, spec, n_tiles, height, width, src_ptr, out, stream=None):
+        """dswx_burn_device: the records at `verts_ptr` (device, 16 bytes each) shared out by the device table int64
+        [n_tiles + 1] at `tile_first_ptr`, burnt by `spec` (a burn.Spec; include/dswx_hip.h "burn", proteus_amd/burn.py states the
+        definition in numpy) -> the outputs `out` names (a BurnOut of device addresses), with the optional device plane at
+        `src_ptr` (which may be out.mask); two memsets and two launches, asynchronous."""
+        _check(self.lib.dswx_burn_device(self.handle, ctypes.c_void_p(verts_ptr) if verts_ptr else None,
+                                         ctypes.c_void_p(tile_first_ptr) if tile_first_ptr else None, ctypes.byref(BurnSpec.of(spec)),
+                                         int(n_tiles), int(height), int(width), ctypes.c_void_p(src_ptr) if src_ptr else None,
+                                         ctypes.byref(out), _stream_arg(stream)))
+
+    def burn(self, verts, tile_first, height, width, spec, src=None, want=('acc', 'mask', 'head'), stream=None):
+        """Rings burnt onto new device planes: uploads the host records `verts` (burn.VERTEX_DTYPE) and the table `tile_first`
+        (int64 [n_tiles + 1]), allocates the wanted outputs and 'acc' always, queues dswx_burn_device on `stream` and waits
+        for it, since the uploaded records are freed on return.  `src` (None, or a host plane uint8 [n_tiles, H, W], or
+        [n_tiles, spec.mask_tile_stride]) is uploaded INTO 'mask' and burnt in place.  Returns {output: DeviceBuffer}: 'acc'
+        uint32 [n_tiles][H*W], 'mask' uint8 [n_tiles][mask_tile_stride or H*W], 'head' uint64 [n_tiles][8] -- device buffers
+        owned by the caller."""
+        verts, tile_first, n = _burn_input(verts, tile_first)
+        want = _burn_wanted(want)
+        if src is not None and 'mask' not in want:
+            raise ValueError("src without 'mask'")
+        if src is not None and spec.src_tile_stride != spec.mask_tile_stride:
+            raise ValueError('src is burnt in place here: src_tile_stride must equal mask_tile_stride')
+        res = _malloc_planes(self, {k: (_burn_shape(k, n, height, width, spec), BURN_DTYPES[k]) for k in want})
+        dv, df = self.malloc(max(verts.nbytes, 16)), self.malloc(tile_first.nbytes)
+        try:
+            with _owned(res):
+                if verts.nbytes:
+                    dv.upload(verts)
+                df.upload(tile_first)
+                if src is not None:
+                    src = np.ascontiguousarray(src, dtype=np.uint8)
+                    if src.size != int(np.prod(_burn_shape('mask', n, height, width, spec), dtype=np.int64)):
+                        raise DswxError(ERR_ARG, f'src has {src.size} bytes, mask {_burn_shape("mask", n, height, width, spec)}')
+                    if src.nbytes:
+                        res['mask'].upload(src)
+                self.burn_device(dv.ptr, df.ptr, spec, n, height, width, res['mask'].ptr if src is not None else None,
+                                 BurnOut.of(**{k: b.ptr for k, b in res.items()}), stream)
+                self.synchronize(stream)
+        finally:
+            dv.free()
+            df.free()
+        return res
+
     def h2d_async(self, dst_ptr, host_arr, nbytes=None, stream=None):
         _check(self.lib.dswx_memcpy_h2d_async(self.handle, ctypes.c_void_p(dst_ptr), _host_ptr(host_arr),
                                               int(host_arr.nbytes if nbytes is None else nbytes),
@@ -1438,6 +1511,57 @@ def outline_host(ids, spec, want=('chain', 'rings', 'head')):
     out = OutlineOut.of(**{k: a.ctypes.data for k, a in res.items()})
     _check(load_library().dswx_outline_host(_host_ptr(ids) if ids.size else None, ctypes.byref(OutlineSpec.of(spec)), n, H, W,
                                             ctypes.byref(out)))
+    return res
+
+
+BURN_DTYPES = {'acc': np.uint32, 'mask': np.uint8, 'head': np.uint64}
+
+
+def _burn_wanted(want):
+    """`want` in the order of the struct; 'acc' is always made (it is the working array)."""
+    want = _wanted(want, BURN_DTYPES)
+    return tuple(k for k in BURN_DTYPES if k == 'acc' or k in want)
+
+
+def _burn_shape(k, n, H, W, spec):
+    return {'acc': (n, H, W), 'mask': (n, spec.mask_tile_stride) if spec.mask_tile_stride else (n, H, W), 'head': (n, BURN_HEAD_WORDS)}[k]
+
+
+def _burn_input(verts, tile_first):
+    """(records as contiguous burn.VERTEX_DTYPE, table as contiguous int64, n_tiles)."""
+    from .burn import VERTEX_DTYPE
+    verts = np.ascontiguousarray(verts)
+    if verts.dtype != VERTEX_DTYPE or verts.ndim != 1:
+        raise ValueError(f'records are burn.VERTEX_DTYPE [k], not {verts.dtype} {verts.shape}')
+    tile_first = np.ascontiguousarray(tile_first, dtype=np.int64)
+    if tile_first.ndim != 1 or len(tile_first) < 1:
+        raise ValueError(f'tile_first is int64 [n_tiles + 1], not {tile_first.shape}')
+    return verts, tile_first, len(tile_first) - 1
+
+
+def burn_host(verts, tile_first, height, width, spec, src=None, want=('acc', 'mask', 'head'), mask=None):
+    """dswx_burn_host (no device needed): the outputs of proteus_amd.burn.burn_tiles named in `want`, and 'acc' always, of the
+    host records `verts` (burn.VERTEX_DTYPE) shared out by `tile_first` (int64 [n_tiles + 1]), by the library's scalar
+    statement.  'mask' is uint8 [n_tiles, H, W], or [n_tiles, spec.mask_tile_stride] with a stride; `mask` names an array of
+    that size to write into instead of a new one (the bytes between the rasters are left as they are), and `src` (uint8, of
+    the size the spec's src stride implies) may be that very array: burnt in place."""
+    verts, tile_first, n = _burn_input(verts, tile_first)
+    want = _burn_wanted(want)
+    res = {k: np.zeros(_burn_shape(k, n, height, width, spec), dtype=BURN_DTYPES[k]) for k in want if not (k == 'mask' and mask is not None)}
+    if mask is not None:
+        if 'mask' not in want or mask.dtype != np.uint8 or not mask.flags.c_contiguous or \
+                mask.size != int(np.prod(_burn_shape('mask', n, height, width, spec), dtype=np.int64)):
+            raise ValueError("mask= is a contiguous uint8 array of the size of the 'mask' output, and 'mask' is wanted")
+        res['mask'] = mask
+    if src is not None:
+        if src is not mask:
+            src = np.ascontiguousarray(src, dtype=np.uint8)
+        if src.size != n * (spec.src_tile_stride or height * width):
+            raise ValueError(f'src has {src.size} bytes, not {n} tiles of {spec.src_tile_stride or height * width}')
+    dummy = np.zeros(1, dtype=verts.dtype)
+    out = BurnOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_burn_host(_host_ptr(verts if verts.size else dummy), _host_ptr(tile_first), ctypes.byref(BurnSpec.of(spec)),
+                                         n, int(height), int(width), _host_ptr(src) if src is not None else None, ctypes.byref(out)))
     return res
 
 
@@ -1764,6 +1888,41 @@ class DeviceBatch:
         res = self.label(name, label_spec, tile0, n_tiles, want=('label',), stream=stream)
         with _owned(res, (DswxError, ValueError)):
             res.update(self.ctx.outline(res['label'], spec, self._tiles(tile0, n_tiles)[1], self.height, self.width, stream=stream))
+        return res
+
+    def burn(self, name, verts, tile_first, spec, tile0=0, n_tiles=None, want=('acc', 'head'), stream=None):
+        """dswx_batch_burn: the records `verts` shared out by `tile_first` (int64 [n_tiles + 1], entry 0 = tile0) burnt INTO
+        the uint8 plane `name` of tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) by `spec` (a burn.Spec
+        with both strides 0) -- the one entry that writes a plane of the batch; 'ocean' in front of classify() is the natural
+        use.  `verts` and `tile_first` are host arrays (uploaded, the call then waits for `stream` before it frees them) or
+        DeviceBuffers / device addresses (asynchronous).  Returns {output: DeviceBuffer}: 'acc' uint32 [n_tiles][H*W] always
+        (the working array), 'head' uint64 [n_tiles][8] when wanted -- device planes owned by the caller.
+        proteus_amd.burn.burn_tiles with src = the downloaded plane gives the same plane and the same outputs."""
+        plane = _plane_index(name)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
+        want = _burn_wanted(tuple(want) + ('acc',))
+        if 'mask' in want:
+            raise ValueError("'mask' is the plane of the batch here")
+        res = _malloc_planes(self.ctx, {k: ((nt, BURN_HEAD_WORDS if k == 'head' else self.n_pixels), BURN_DTYPES[k]) for k in want})
+        temps = []
+        try:
+            with _owned(res):
+                if isinstance(verts, np.ndarray) or isinstance(tile_first, np.ndarray):
+                    verts, tile_first, _ = _burn_input(verts, tile_first)
+                    temps = [self.ctx.malloc(max(verts.nbytes, 16)), self.ctx.malloc(tile_first.nbytes)]
+                    if verts.nbytes:
+                        temps[0].upload(verts)
+                    temps[1].upload(tile_first)
+                    verts, tile_first = temps
+                _check(self.ctx.lib.dswx_batch_burn(self.handle, plane, ctypes.c_void_p(getattr(verts, 'ptr', verts)),
+                                                    ctypes.c_void_p(getattr(tile_first, 'ptr', tile_first)), ctypes.byref(BurnSpec.of(spec)),
+                                                    ctypes.c_void_p(res['acc'].ptr), ctypes.c_void_p(res['head'].ptr) if 'head' in res else None,
+                                                    int(tile0), n_tiles, _stream_arg(stream)))
+                if temps:
+                    self.ctx.synchronize(stream)
+        finally:
+            for b in temps:
+                b.free()
         return res
 
     def read_tile(self, name, tile):

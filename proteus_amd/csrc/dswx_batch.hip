@@ -98,7 +98,7 @@ static void bind_structs(const dswx_batch* b, dswx_planes_in_t* in, dswx_planes_
         if (d.batch >= 0) dswx_plane_set(d, in, out, b->ptr[d.batch]);
 }
 
-// ---- The pieces of the entries that work on resident planes (dswx_batch_checksum ... dswx_batch_distance below); the rules
+// ---- The pieces of the entries that work on resident planes (dswx_batch_checksum ... dswx_batch_burn below); the rules
 // themselves are in dswx_batch_select.h.
 static dswx_batch_view view_of(const dswx_batch* b) {
     return {b->geom.n_tiles, b->geom.height, b->geom.width, b->geom.tile_stride, b->device, b->ptr};
@@ -520,6 +520,26 @@ int dswx_batch_distance(dswx_batch_t* b, int32_t plane, const dswx_distance_spec
     dswx_ctx* ctx = b->ctx;
     HIP_TRY(hipSetDevice(ctx->device));
     return dswx_distance_launch(ctx, base, spec, n_tiles, v.height, v.width, stride, out, dswx_stream_of(ctx, stream));
+}
+
+// Polygon rings burnt INTO one uint8 plane of a resident batch (dswx_burn.hip), asynchronous: the plane is both `mask` and `src`
+// at the batch's stride -- the first entry here that writes a plane of the batch; acc and head are the caller's device memory,
+// so nothing is allocated, copied or waited for here.
+int dswx_batch_burn(dswx_batch_t* b, int32_t plane, const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec,
+                    uint32_t* acc, uint64_t* head, int64_t tile0, int64_t n_tiles, void* stream) {
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not burnt into", "polygons are burnt into a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    if (spec && (spec->mask_tile_stride || spec->src_tile_stride))
+        return dswx_fail(DSWX_ERR_ARG, "mask_tile_stride %lld and src_tile_stride %lld must be 0: the plane has the stride of the batch",
+                         (long long)spec->mask_tile_stride, (long long)spec->src_tile_stride);
+    const dswx_burn_out_t out = {acc, const_cast<uint8_t*>(base), head};
+    int64_t mask_stride, src_stride;
+    if (int rc = dswx_burn_check(verts, tile_first, spec, n_tiles, v.height, v.width, base, &out, &mask_stride, &src_stride, true)) return rc;
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return dswx_burn_launch(ctx, verts, tile_first, spec, n_tiles, v.height, v.width, base, v.tile_stride, v.tile_stride, &out,
+                            dswx_stream_of(ctx, stream));
 }
 
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch

@@ -1,4 +1,4 @@
-// dswx_batch_select.h -- what a resident-batch entry (dswx_batch_checksum ... dswx_batch_distance, dswx_batch.hip) may be
+// dswx_batch_select.h -- what a resident-batch entry (dswx_batch_checksum ... dswx_batch_burn, dswx_batch.hip) may be
 // asked for: which tiles, which planes, and where tile `tile0` of a plane begins.  Plain host functions over a plain view of
 // a batch, no HIP call and nothing dereferenced, so that tests/native/batch_select_host.cpp drives them without a device.
 // Of dswx_host.h they take DSWX_PLANES and dswx_fail.

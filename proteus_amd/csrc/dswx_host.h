@@ -297,6 +297,14 @@ int dswx_distance_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_distanc
 int dswx_outline_launch(dswx_ctx* ctx, const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height,
                         int64_t width, const dswx_outline_out_t* out, void* work, hipStream_t s);
 
+// ---- burn (dswx_burn.hip): the shared checks of the entries (resolves the two strides of the spec, 0 = height * width;
+// `align`: verts must be 16-byte, acc 4-byte and tile_first and head 8-byte aligned), and the launches for arguments that
+// passed them, with the strides given apart from the spec (a batch has its own)
+int dswx_burn_check(const void* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                    const uint8_t* src, const dswx_burn_out_t* out, int64_t* mask_stride, int64_t* src_stride, bool align);
+int dswx_burn_launch(dswx_ctx* ctx, const void* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles, int64_t height,
+                     int64_t width, const uint8_t* src, int64_t mask_stride, int64_t src_stride, const dswx_burn_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

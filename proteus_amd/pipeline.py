@@ -214,6 +214,47 @@ class DevicePlane:
             self.engine._give(work)
         return made
 
+    def burn(self, polygons_px, spec=None, words=None, want=('acc', 'head')):
+        """Polygon rings burnt INTO this [n, H, W] (or one [H, W]) uint8 plane as it lies in HBM (dswx_burn_device with the
+        plane as both `src` and `mask`; proteus_amd.burn.burn_tiles with src = the same array gives the same plane): the
+        pixels whose centre is inside by the even-odd rule become spec.burn (a burn.Spec, default 1), every other pixel stays.
+        `polygons_px` is a list of rings -- [k, 2] arrays of (x, y) in PIXEL coordinates, (0, 0) the top left corner of the
+        raster, floats allowed, the closing point not repeated -- for an [H, W] plane, and a list of such lists, one per tile,
+        for an [n, H, W] plane; ring j toggles words[j] (same nesting; default 1: rings that overlap cancel, so give every
+        polygon a bit of its own, holes the bit of their polygon, where polygons may overlap).  Returns a dict of DevicePlanes
+        'acc' uint32 [n, H, W] (always) and 'head' uint64 [n, 8], which stay on the device.  16 bytes per vertex cross PCIe,
+        not a plane."""
+        from . import burn as _burn
+        if len(self.shape) not in (2, 3) or self.dtype != np.uint8:
+            raise ValueError(f'polygons are burnt into a uint8 [n, H, W] or [H, W] plane, not {self.dtype} {self.shape}')
+        spec = _burn.Spec() if spec is None else spec
+        if spec.mask_tile_stride or spec.src_tile_stride:
+            raise ValueError('the strides of the spec must be 0: the plane is dense')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        if len(self.shape) == 2:
+            polygons_px, words = [polygons_px], [words]
+        elif words is None:
+            words = [None] * n_tiles
+        if len(polygons_px) != n_tiles or len(words) != n_tiles:
+            raise ValueError(f'{len(polygons_px)} lists of rings for {n_tiles} tiles')
+        verts, first = _burn.tiles([_burn.records([_burn.quantise(np.asarray(p, dtype=np.float64).reshape(-1, 2)) for p in rings], w)
+                                    for rings, w in zip(polygons_px, words)])
+        made = {k: self.engine.plane((n_tiles, _capi.BURN_HEAD_WORDS) if k == 'head' else (n_tiles, height, width), _capi.BURN_DTYPES[k])
+                for k in _capi._burn_wanted(tuple(want) + ('acc',)) if k != 'mask'}
+        d_verts = self.engine.upload(verts.view(np.uint32).reshape(-1, 4) if len(verts) else np.zeros((1, 4), dtype=np.uint32))
+        d_first = self.engine.upload(first)
+        try:
+            out = _capi.BurnOut.of(mask=self.ptr, **{k: p.ptr for k, p in made.items()})
+            with self.engine.lock, stages.span('gpu: burn'):
+                self.engine.ctx.burn_device(d_verts.ptr, d_first.ptr, spec, n_tiles, height, width, self.ptr, out)
+                self.engine.ctx.synchronize()
+        finally:
+            d_verts.release()
+            d_first.release()
+        self._host = None                                    # (the raster changed under a copy kept by numpy())
+        return made
+
     def body_table(self, spec, value=None, want=('dense', 'rows', 'head')):
         """The bodies of this LABEL plane -- uint32 [n, H, W] (or one [H, W]) as label(...)['label'] leaves it in HBM --
         renumbered 1 .. K and tabulated (dswx_body_table_device; proteus_amd.bodies.body_table of the same arrays gives the
