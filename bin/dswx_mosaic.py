@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""`dswx_mosaic.py [--band N] [--no-partial] [--device N] [--bodies FILE.json] -o PREFIX file1.tif file2.tif ...`
+
+Neighbouring tiles, and several dates of them, placed on one canvas and composited per canvas pixel on the GPU
+(include/dswx_hip.h "mosaic"): band N (default 1 = WTR) of every DSWx-HLS product file is read into one resident [n, H, W]
+plane, the geotransforms place every file on the lattice of the first (proteus_amd.mosaic.layout: the canvas is the bounding
+box of the footprints), and one kernel launch turns the plane into
+
+    PREFIX_COUNT_WATER.tif   UInt16  on how many covering files the pixel was water (open or, unless --no-partial, partial)
+    PREFIX_COUNT_LAND.tif    UInt16  on how many it was clear and not water
+    PREFIX_LAST.tif          Byte    its latest clear observation, in the order of the files (nodata 255, WTR colours); a pixel
+                                     outside every footprint is 255 too
+    PREFIX_LAST_INDEX.tif    UInt16  which file (0 = the first) that observation came from (nodata 65535)
+    PREFIX_SHARE.tif         Byte    100 * water / (water + land) in integer division: surface water occurrence (nodata 255)
+
+written as COGs with the geotransform of the canvas by the product writer.  The files are given in priority / time order: where
+footprints overlap, the LAST file that saw the pixel clear gives LAST.  They must be of one size and one projection (the
+GeoKey tags are compared) and lie on one lattice of whole pixels: nothing is resampled or reprojected, so a neighbour in
+another UTM zone is refused.  With --bodies FILE.json the water bodies of the LAST canvas are labelled on the GPU
+(include/dswx_hip.h "label") and the summary is written to FILE.json and printed as one line of JSON: a lake on a seam is ONE
+body.  PROTEUS has no such tool: there is no reference output to be equal to; proteus_amd/mosaic.py states what the layers are.
+"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np   # noqa: E402
+
+from proteus_amd import dswx_hls, geotiff, pipeline   # noqa: E402
+from proteus_amd.label import wtr_label_spec   # noqa: E402
+from proteus_amd.mosaic import layout, wtr_mosaic_spec   # noqa: E402
+from proteus_amd.stack import MAX_TILES, NONE, NO_SHARE   # noqa: E402
+
+_spec = importlib.util.spec_from_file_location('dswx_stack_tool', os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dswx_stack.py'))
+_stack_tool = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_stack_tool)
+read_stack = _stack_tool.read_stack
+
+PROJECTION_TAGS = (geotiff.TAG_GEOKEYS, geotiff.TAG_GEO_DOUBLES, geotiff.TAG_GEO_ASCII)
+
+
+def place_files(infos):
+    """(canvas_h, canvas_w, place, canvas geotransform, canvas geo tags) of the files; refused: another projection than the
+    first file's, and what proteus_amd.mosaic.layout refuses."""
+    first = infos[0]
+    for k, info in enumerate(infos):
+        for tag in PROJECTION_TAGS:
+            a, b = first.geo_tags.get(tag), info.geo_tags.get(tag)
+            if (a is None) != (b is None) or (a is not None and (a[0] != b[0] or list(a[1]) != list(b[1]))):
+                raise ValueError(f'[FAIL] Comparing projection\n       * input 1 GeoTIFF tag {tag} with content "{a}" differs from input '
+                                 f'{k + 1} GeoTIFF tag {tag} with content "{b}".')
+    try:
+        canvas_h, canvas_w, place, gt = layout([tuple(float(v) for v in i.geotransform) for i in infos], first.height, first.width)
+    except ValueError as e:
+        raise ValueError(f'[FAIL] Comparing geotransform\n       * {e}.') from None
+    tags = dict(first.geo_tags)
+    tags.pop(geotiff.TAG_TRANSFORM, None)
+    tags.update({k: v for k, v in geotiff.geo_tags_from_geotransform(gt).items()})
+    return canvas_h, canvas_w, place, gt, tags
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description='Mosaic neighbouring tiles and their dates per canvas pixel: water counts, latest '
+                                             'clear observation, surface water occurrence')
+    ap.add_argument('input_file', type=str, nargs='+', help='DSWx-HLS product files of one size on one lattice, in priority / time order')
+    ap.add_argument('-o', '--output-prefix', dest='prefix', type=str, required=True, help='PREFIX of the five output files')
+    ap.add_argument('--band', type=int, default=1, metavar='N', help='band of the product files to mosaic (default 1 = WTR)')
+    ap.add_argument('--no-partial', action='store_true', help='partial surface water counts as clear and not water')
+    ap.add_argument('--bodies', type=str, default=None, metavar='FILE.json', help='label the water bodies of LAST, write the summary')
+    ap.add_argument('--device', type=int, default=None, metavar='N', help='GPU to run on (default $DSWX_DEVICE or 0)')
+    args = ap.parse_args(argv)
+    for f in args.input_file:
+        if not os.path.isfile(f):
+            print(f'ERROR file not found: {f}')
+            return 1
+    if len(args.input_file) > MAX_TILES:
+        print(f'ERROR {len(args.input_file)} files: at most {MAX_TILES}')
+        return 1
+    engine = pipeline.engine_of(dswx_hls.get_context(args.device))
+    infos = []
+    try:
+        plane, info = read_stack(engine, args.input_file, args.band, same_geotransform=False, infos=infos)
+    except ValueError as e:
+        print(e)
+        return 1
+    try:
+        canvas_h, canvas_w, place, gt, tags = place_files(infos)
+    except ValueError as e:
+        plane.release()
+        print(e)
+        return 1
+    spec = wtr_mosaic_spec(collapsed=True, partial_is_water=not args.no_partial, fill=dswx_hls.UINT8_FILL_VALUE,
+                           outside=dswx_hls.UINT8_FILL_VALUE)
+    res = plane.mosaic(place, (canvas_h, canvas_w), spec)
+    plane.release()
+    md = dict(info.metadata)
+    md['MOSAIC_INPUT_FILES'] = ', '.join(os.path.basename(f) for f in args.input_file)
+    md['MOSAIC_INPUT_BAND'] = str(args.band)
+    md['MOSAIC_PARTIAL_SURFACE_WATER_IS_WATER'] = str(not args.no_partial)
+    md['MOSAIC_PLACEMENTS_ROW_COL'] = ', '.join(f'{int(r)} {int(c)}' for r, c in place)
+    said = None
+    if args.bodies is not None:
+        lab = res['last'].label(wtr_label_spec(1, partial_is_water=not args.no_partial), want=('summary',))
+        s = [int(v) for v in lab['summary'].numpy()[0]]
+        for p in lab.values():
+            p.release()
+        said = {'input_files': [os.path.basename(f) for f in args.input_file], 'band': args.band, 'canvas_height': canvas_h,
+                'canvas_width': canvas_w, 'bodies': s[0], 'member_pixels': s[1], 'largest_size': s[2], 'largest_label': s[3],
+                'bodies_by_log2_size': s[8:], 'pixel_area_m2': abs(gt[1] * gt[5])}
+    outputs = (('count0', 'COUNT_WATER', 'Number of covering files with water', None, None),
+               ('count1', 'COUNT_LAND', 'Number of clear covering files without water', None, None),
+               ('last', 'LAST', 'Latest clear observation', dswx_hls._get_interpreted_dswx_ctable(True, layer_name='WTR'),
+                dswx_hls.UINT8_FILL_VALUE),
+               ('last_index', 'LAST_INDEX', 'Index of the file of the latest clear observation', None, NONE),
+               ('share', 'SHARE', 'Surface water occurrence in percent of the clear covering files', None, NO_SHARE))
+    written = []
+    for key, suffix, description, ctable, nodata in outputs:
+        dswx_hls._save_array(res[key], f'{args.prefix}_{suffix}.tif', md, tags, description=description,
+                             output_files_list=written, ctable=ctable, no_data_value=nodata)
+    for p in res.values():
+        p.release()
+    if said is not None:
+        with open(args.bodies, 'w') as f:
+            json.dump(said, f)
+        written.append(args.bodies)
+    for f in written:
+        print(f'file saved: {f}')
+    if said is not None:
+        print(json.dumps(said))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -25,9 +25,10 @@ from proteus_amd import dswx_hls, pipeline   # noqa: E402
 from proteus_amd.stack import MAX_TILES, NONE, NO_SHARE, wtr_spec   # noqa: E402
 
 
-def read_stack(engine, files, band):
+def read_stack(engine, files, band, same_geotransform=True, infos=None):
     """The band of every file -> (DevicePlane uint8 [n, H, W], GeoTiffInfo of the first file); files whose size or
-    geotransform differ from the first are refused."""
+    geotransform differ from the first are refused.  same_geotransform=False leaves the geotransforms to the caller
+    (bin/dswx_mosaic.py), who finds the GeoTiffInfo of every file appended to the list `infos`."""
     stack = first = None
     for k, path in enumerate(files):
         plane, info = engine.read_bands(path)
@@ -42,7 +43,9 @@ def read_stack(engine, files, band):
             if (info.height, info.width) != (first.height, first.width):
                 raise ValueError(f'[FAIL] Comparing size\n       * input 1 has size "{first.width} x {first.height}" whereas input '
                                  f'{k + 1} has size "{info.width} x {info.height}".')
-            if not np.array_equal(info.geotransform, first.geotransform):
+            if infos is not None:
+                infos.append(info)
+            if same_geotransform and not np.array_equal(info.geotransform, first.geotransform):
                 raise ValueError(f'[FAIL] Comparing geotransform\n       * input 1 geotransform with content "{first.geotransform}" '
                                  f'differs from input {k + 1} geotransform with content "{info.geotransform}".')
             n = info.height * info.width

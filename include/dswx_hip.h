@@ -1267,6 +1267,62 @@ int dswx_batch_burn(dswx_batch_t* batch, int32_t plane, const dswx_burn_vertex_t
 int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles,
                    int64_t height, int64_t width, const uint8_t* src, const dswx_burn_out_t* out_host);
 
+/* ---- mosaic: tiles placed on one canvas and composited per canvas pixel -- a stack with placements (additive to ABI v7) ---
+ * Every entry above treats a tile on its own, and a stack requires every tile to cover the same pixels.  Neighbouring MGRS
+ * tiles of one UTM zone share the 30 m lattice and overlap by about 326 pixels: a lake on a seam is two bodies until the tiles
+ * are placed relative to each other.  These entries do that without a plane crossing PCIe.  The result is a canvas plane in
+ * device memory, and the entries that take a caller's plane of any height x width (label, body table, distance, outline, grid,
+ * histogram) work across the seams unchanged.  Several dates of several neighbours give the latest clear observation and the
+ * surface-water occurrence per canvas pixel.  A C caller tests for the entries with DSWX_HAS_MOSAIC.
+ * THE DEFINITION.  The input is one uint8 plane [n_tiles][tile_stride] at any address; every tile is a raster of height x
+ * width with row pitch `width`, and the padding up to the stride is never read.  place = int32 [n_tiles][2] = (row0, col0),
+ * the canvas position of pixel (0, 0) of the tile; ANY content is legal.  The canvas is canvas_h x canvas_w, dense, row pitch
+ * canvas_w.  Tile t COVERS canvas pixel (Y, X) iff 0 <= Y - row0[t] < height and 0 <= X - col0[t] < width, evaluated in 64
+ * bits (INT32_MIN and INT32_MAX are ordinary values).  Tiles may overlap, coincide, hang over any edge of the canvas, lie
+ * wholly outside it (ignored) or be larger than it.  Per canvas pixel the rule of a stack (above) is applied, unchanged, over
+ * the COVERING tiles in increasing t: count[k], last, last_index (the index t in the plane, not a rank among the covering
+ * tiles) and share.  A pixel that is covered but never observed gets `fill`, DSWX_STACK_NONE, DSWX_STACK_NO_SHARE and counts
+ * 0, as in a stack; a pixel that NO tile covers gets the same values except last = `outside`.  n_tiles <=
+ * DSWX_STACK_MAX_TILES; n_tiles == 0 writes the outside values; an empty canvas writes nothing; an empty tile raster covers
+ * nothing.  canvas_h, canvas_w <= 2^30.  All of it is integer arithmetic per pixel: the result is deterministic and
+ * independent of the launch geometry.
+ * THE LIMITS THAT REMAIN.  The tiles of one plane share a size, and placement is in whole pixels of ONE lattice: nothing is
+ * resampled or reprojected, so a neighbour in another UTM zone is still refused by the tools. */
+#define DSWX_HAS_MOSAIC 1
+typedef struct dswx_mosaic_spec {
+    int32_t n_cats;                    /* 1 .. DSWX_STACK_MAX_CATS */
+    int32_t fill;                      /* 0 .. 255: `last` of a pixel that is covered but that no tile observed */
+    int32_t outside;                   /* 0 .. 255: `last` of a pixel that no tile covers */
+    int32_t reserved;                  /* must be 0 */
+    uint8_t cat_of_byte[256];          /* as in dswx_stack_spec_t */
+} dswx_mosaic_spec_t;                  /* 272 bytes */
+/* One plane [n_tiles][tile_stride_elems] in DEVICE memory, placed by place_device (DEVICE memory, read by the device only) ->
+ * the wanted planes of *out_device (device memory, canvas_h * canvas_w elements each).  Asynchronous on `stream` (NULL = the
+ * context's stream): ONE kernel launch, no synchronisation, no scratch of the context, no allocation, no memset; every wanted
+ * output element is written exactly once and nothing else is written.  tile_stride_elems 0 = height * width.  The refusals of
+ * dswx_stack_device (with height * width for n_elems), and: `outside` outside 0 .. 255, reserved != 0, a negative height,
+ * width or canvas size, a tile side or a canvas side above 2^30, a canvas above 2^46 pixels or above what one launch covers
+ * (2^36 pixels), a NULL place_device with n_tiles > 0: DSWX_ERR_ARG; place_device off 4 bytes: DSWX_ERR_ALIGN.  (The
+ * arguments are checked before the context is, and a refused call writes nothing; the limits on the size of the plane are
+ * those of dswx_compare_device.)  The output planes MUST NOT OVERLAP the plane, the table or each other: NOT CHECKED. */
+int dswx_mosaic_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64_t n_tiles, int64_t height,
+                       int64_t width, int64_t tile_stride_elems, const int32_t* place_device, int64_t canvas_h, int64_t canvas_w,
+                       const dswx_stack_out_t* out_device, void* stream);
+/* Plane `plane` (a uint8 DSWX_PLANE_* of the library's plane table) of a resident batch, tiles tile0 .. tile0 + n_tiles - 1
+ * (n_tiles DSWX_BATCH_ALL_TILES = up to the last) placed by place_device, whose entry 0 belongs to tile0 -> the wanted planes
+ * of *out_device: device planes of canvas_h x canvas_w elements owned by the caller.  last_index counts from tile0, as that of
+ * dswx_batch_stack does.  Asynchronous on `stream` (NULL = the stream of the batch's context) like dswx_mosaic_device.
+ * Planes and tile ranges: the rules of dswx_batch_stack. */
+int dswx_batch_mosaic(dswx_batch_t* batch, int32_t plane, const dswx_mosaic_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                      const int32_t* place_device, int64_t canvas_h, int64_t canvas_w, const dswx_stack_out_t* out_device,
+                      void* stream);
+/* The same definition on HOST buffers in plain scalar C++, with a HOST place table: needs no device and no context.  The
+ * other half of a comparison, not a fallback of the two entries above.  The refusals of dswx_mosaic_device, except that every
+ * buffer, the table and the uint16 planes included, may sit at any address. */
+int dswx_mosaic_host(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                     int64_t tile_stride_elems, const int32_t* place_host, int64_t canvas_h, int64_t canvas_w,
+                     const dswx_stack_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1295,7 +1351,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -48,7 +48,8 @@ EXPORTED_SYMBOLS = (
     'dswx_body_table_device', 'dswx_batch_body_table', 'dswx_body_table_host',
     'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host',
     'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host',
-    'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host')
+    'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host',
+    'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -79,6 +80,11 @@ BURN_HEAD_WORDS, BURN_MAX_COORD = 8, 1 << 30
 # csrc/dswx_burn_rule.h: the rows of an edge that its own thread finishes (a longer edge is shared out over the wave) and the
 # pixels of a row that a wave of the scan launch takes per step (tests build shapes around the seams)
 BURN_THREAD_ROWS, BURN_SCAN_STEP = 4, 256
+HAS_MOSAIC = 1                    # DSWX_HAS_MOSAIC: additive to ABI v7
+# csrc/dswx_mosaic.hip: the rows and the columns of the canvas rectangle of one workgroup, the tiles of the surviving-tile list
+# in LDS, the placements tested per step and the loads in flight per thread (tests build shapes around the seams)
+MOSAIC_RECT_H, MOSAIC_RECT_W, MOSAIC_LIST, MOSAIC_CHUNK, MOSAIC_ROUND = 4, 1024, 512, 256, 8
+MOSAIC_MAX_SIDE = 1 << 30
 
 
 class DswxError(RuntimeError):
@@ -194,6 +200,18 @@ class StackOut(ctypes.Structure):
         for k, p in enumerate(count):
             c.count[k] = p or None
         c.last, c.last_index, c.share = last or None, last_index or None, share or None
+        return c
+
+
+class MosaicSpec(ctypes.Structure):
+    """dswx_mosaic_spec_t; proteus_amd.mosaic.Spec is the Python form."""
+    _fields_ = [('n_cats', ctypes.c_int32), ('fill', ctypes.c_int32), ('outside', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('cat_of_byte', ctypes.c_uint8 * 256)]
+
+    @classmethod
+    def of(cls, spec):
+        c = cls(spec.n_cats, spec.fill, spec.outside, getattr(spec, 'reserved', 0))
+        ctypes.memmove(c.cat_of_byte, spec.cat_of_byte.ctypes.data, 256)
         return c
 
 
@@ -501,6 +519,9 @@ def load_library(path=None):
         'dswx_stack_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
         'dswx_batch_stack': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_stack_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp]),
+        'dswx_mosaic_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
+        'dswx_batch_mosaic': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, i64, i64, vp, vp]),
+        'dswx_mosaic_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp]),
         'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
@@ -1143,6 +1164,15 @@ class Context:
                                           int(n_elems), int(tile_stride), ctypes.byref(out),
                                           _stream_arg(stream)))
 
+    def mosaic_device(self, plane_ptr, spec, n_tiles, height, width, place_ptr, canvas_h, canvas_w, out, tile_stride=0, stream=None):
+        """dswx_mosaic_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, placed on a
+        canvas_h x canvas_w canvas by the device table int32 [n_tiles][2] at place_ptr and composited per canvas pixel by `spec`
+        (a mosaic.Spec; include/dswx_hip.h "mosaic", proteus_amd/mosaic.py states the definition in numpy) -> the planes `out`
+        names (a StackOut of device addresses, canvas_h * canvas_w elements each); one launch, asynchronous."""
+        _check(self.lib.dswx_mosaic_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(MosaicSpec.of(spec)), int(n_tiles),
+                                           int(height), int(width), int(tile_stride), ctypes.c_void_p(place_ptr), int(canvas_h),
+                                           int(canvas_w), ctypes.byref(out), _stream_arg(stream)))
+
     def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
         onto cells by `spec` (a grid.Spec; include/dswx_hip.h "grid", proteus_amd/grid.py states the definition in numpy) ->
@@ -1349,6 +1379,22 @@ def stack_host(tiles, spec, want=('count', 'last', 'last_index', 'share')):
                       **{k: res[k].ctypes.data for k in ('last', 'last_index', 'share') if k in res})
     _check(load_library().dswx_stack_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(StackSpec.of(spec)), T, n, 0,
                                           ctypes.byref(out)))
+    return res
+
+
+def mosaic_host(tiles, place, canvas_shape, spec, want=('count', 'last', 'last_index', 'share'), raster=None):
+    """dswx_mosaic_host (no device needed): the planes of proteus_amd.mosaic.mosaic_tiles -- those named in `want` -- of a
+    host plane uint8 [n_tiles, H, W] placed by `place` (int32 [n_tiles, 2] = row0, col0) on a canvas of canvas_shape, by the
+    library's scalar statement of the definition.  With raster=(H, W), `tiles` is a padded plane uint8 [n_tiles, tile_stride],
+    tile_stride >= H * W, whose padding is not read."""
+    tiles, n, H, W, stride = _host_plane(tiles, raster)
+    place = np.ascontiguousarray(place, dtype=np.int32).reshape(n, 2)
+    ch, cw = (int(v) for v in canvas_shape)
+    res = _stack_planes(want, spec, (max(ch, 0), max(cw, 0)), lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = StackOut.of(count=[c.ctypes.data for c in res['count']] if 'count' in res else (),
+                      **{k: res[k].ctypes.data for k in ('last', 'last_index', 'share') if k in res})
+    _check(load_library().dswx_mosaic_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(MosaicSpec.of(spec)), n, H, W,
+                                           stride, _host_ptr(place) if n else None, ch, cw, ctypes.byref(out)))
     return res
 
 
@@ -1806,6 +1852,26 @@ class DeviceBatch:
         with _owned(res):
             _check(self.ctx.lib.dswx_batch_stack(self.handle, plane, ctypes.byref(StackSpec.of(spec)), int(tile0),
                                                  self._tiles(tile0, n_tiles)[0], ctypes.byref(out), _stream_arg(stream)))
+        return res
+
+    def mosaic(self, name, place_ptr, canvas_shape, spec, tile0=0, n_tiles=None, want=('count', 'last', 'last_index', 'share'),
+               stream=None):
+        """dswx_batch_mosaic: tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of the uint8 plane `name`
+        placed on a canvas of canvas_shape = (canvas_h, canvas_w) by the DEVICE table int32 [n_tiles][2] at place_ptr (entry 0
+        belongs to tile0) and composited per canvas pixel by `spec` (a mosaic.Spec), by ONE kernel launch, asynchronous on
+        `stream`.  Returns {output: DeviceBuffer} for the outputs named in `want`: 'count' uint16 [n_cats][canvas_h * canvas_w],
+        'last' uint8, 'last_index' uint16 (counted from tile0) and 'share' uint8 [canvas_h * canvas_w] -- device planes owned by
+        the caller.  proteus_amd.mosaic.mosaic_tiles of the downloaded tiles gives the same planes."""
+        plane = _plane_index(name)
+        ch, cw = (int(v) for v in canvas_shape)
+        n = max(ch * cw, 1)
+        res = _malloc_planes(self.ctx, _stack_planes(want, spec, (n,), lambda shp, dt: (shp, dt)))
+        out = StackOut.of(count=[res['count'].ptr + 2 * n * k for k in range(spec.n_cats)] if 'count' in res else (),
+                          **{k: res[k].ptr for k in ('last', 'last_index', 'share') if k in res})
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_mosaic(self.handle, plane, ctypes.byref(MosaicSpec.of(spec)), int(tile0),
+                                                  self._tiles(tile0, n_tiles)[0], ctypes.c_void_p(place_ptr), ch, cw,
+                                                  ctypes.byref(out), _stream_arg(stream)))
         return res
 
     def grid(self, name, spec, tile0=0, n_tiles=None, want=('count', 'share', 'coverage', 'major'), stream=None):

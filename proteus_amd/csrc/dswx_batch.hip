@@ -542,6 +542,22 @@ int dswx_batch_burn(dswx_batch_t* b, int32_t plane, const dswx_burn_vertex_t* ve
                             dswx_stream_of(ctx, stream));
 }
 
+// The tiles of ONE uint8 plane of a resident batch placed on a canvas and composited per canvas pixel (dswx_mosaic.hip), one
+// launch, asynchronous: the table and the outputs are the caller's device memory, so nothing is allocated, copied or waited
+// for here.  place[0] belongs to tile0, and last_index counts from tile0.
+int dswx_batch_mosaic(dswx_batch_t* b, int32_t plane, const dswx_mosaic_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                      const int32_t* place, int64_t canvas_h, int64_t canvas_w, const dswx_stack_out_t* out, void* stream) {
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not mosaicked", "a mosaic is made of a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    int64_t stride = v.tile_stride;
+    if (int rc = dswx_mosaic_check(base, spec, n_tiles, v.height, v.width, &stride, place, canvas_h, canvas_w, out, true)) return rc;
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return dswx_mosaic_launch(ctx, base, spec, n_tiles, v.height, v.width, stride, place, canvas_h, canvas_w, out,
+                              dswx_stream_of(ctx, stream));
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

@@ -305,6 +305,15 @@ int dswx_burn_check(const void* verts, const int64_t* tile_first, const dswx_bur
 int dswx_burn_launch(dswx_ctx* ctx, const void* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, const uint8_t* src, int64_t mask_stride, int64_t src_stride, const dswx_burn_out_t* out, hipStream_t s);
 
+// ---- mosaic (dswx_mosaic.hip): the shared checks of the entries (resolves a stride of 0; `align`: the uint16 outputs must
+// be 2-byte and the placement table 4-byte aligned), and the launch for arguments that passed them
+int dswx_mosaic_check(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                      int64_t* stride, const int32_t* place, int64_t canvas_h, int64_t canvas_w, const dswx_stack_out_t* out,
+                      bool align);
+int dswx_mosaic_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64_t n_tiles, int64_t height,
+                       int64_t width, int64_t stride, const int32_t* place, int64_t canvas_h, int64_t canvas_w,
+                       const dswx_stack_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

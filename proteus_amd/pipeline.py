@@ -122,6 +122,37 @@ class DevicePlane:
         res.update(made)
         return res
 
+    def mosaic(self, place, canvas_shape, spec, want=('count', 'last', 'last_index', 'share')):
+        """The rasters of a [n, H, W] uint8 plane placed on one canvas of canvas_shape = (canvas_h, canvas_w) by `place` (int
+        [n, 2] = row0, col0 of every raster on the canvas; mosaic.layout makes one from geotransforms) and composited per
+        canvas pixel as they lie in HBM (dswx_mosaic_device; proteus_amd.mosaic.mosaic_tiles of the same arrays gives the same
+        planes): a dict of [canvas_h, canvas_w] DevicePlanes named as those of `stack`, which stay on the device -- 'last' can
+        be labelled, measured, outlined, gridded or written across the seams of the rasters.  `spec` is a mosaic.Spec
+        (mosaic.wtr_mosaic_spec for a WTR layer)."""
+        if len(self.shape) != 3 or self.dtype != np.uint8:
+            raise ValueError(f'a mosaic is made of a uint8 [n, H, W] plane, not {self.dtype} {self.shape}')
+        n_tiles, height, width = self.shape
+        place = np.ascontiguousarray(place, dtype=np.int32)
+        if place.shape != (n_tiles, 2):
+            raise ValueError(f'place has shape {place.shape}, not ({n_tiles}, 2)')
+        shape = tuple(int(v) for v in canvas_shape)
+        if len(shape) != 2 or min(shape) < 0 or max(shape) > _capi.MOSAIC_MAX_SIDE:
+            raise ValueError(f'a canvas is (canvas_h, canvas_w) with sides 0 .. {_capi.MOSAIC_MAX_SIDE}, not {canvas_shape}')
+        made = _capi._stack_planes(want, spec, shape, lambda shp, dt: [self.engine.plane(shape, dt) for _ in range(shp[0])]
+                                   if len(shp) == 3 else self.engine.plane(shp, dt))
+        out = _capi.StackOut.of(count=[p.ptr for p in made.get('count', ())],
+                                **{k: made[k].ptr for k in ('last', 'last_index', 'share') if k in made})
+        table = self.engine.upload(place if n_tiles else np.zeros((1, 2), dtype=np.int32))
+        try:
+            with self.engine.lock, stages.span('gpu: mosaic'):
+                self.engine.ctx.mosaic_device(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
+                self.engine.ctx.synchronize()
+        finally:
+            table.release()
+        res = {f'count{k}': p for k, p in enumerate(made.pop('count', ()))}
+        res.update(made)
+        return res
+
     def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
         """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;
         proteus_amd.grid.grid_tiles of the same array gives the same planes): a dict of [n, GH, GW] DevicePlanes for the
