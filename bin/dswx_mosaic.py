@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`dswx_mosaic.py [--band N] [--no-partial] [--device N] [--bodies FILE.json] -o PREFIX file1.tif file2.tif ...`
+"""`dswx_mosaic.py [--band N] [--no-partial] [--reproject] [--device N] [--bodies FILE.json] -o PREFIX file1.tif file2.tif ...`
 
 Neighbouring tiles, and several dates of them, placed on one canvas and composited per canvas pixel on the GPU
 (include/dswx_hip.h "mosaic"): band N (default 1 = WTR) of every DSWx-HLS product file is read into one resident [n, H, W]
@@ -15,8 +15,12 @@ box of the footprints), and one kernel launch turns the plane into
 
 written as COGs with the geotransform of the canvas by the product writer.  The files are given in priority / time order: where
 footprints overlap, the LAST file that saw the pixel clear gives LAST.  They must be of one size and one projection (the
-GeoKey tags are compared) and lie on one lattice of whole pixels: nothing is resampled or reprojected, so a neighbour in
-another UTM zone is refused.  With --bodies FILE.json the water bodies of the LAST canvas are labelled on the GPU
+GeoKey tags are compared) and lie on one lattice of whole pixels: without --reproject nothing is resampled or reprojected, so a
+neighbour in another UTM zone is refused.  With --reproject an input whose GeoKeys name another WGS 84 / UTM zone, or whose
+origin or pixel size is off the lattice of input 1, is first resampled on the GPU (nearest pixel; include/dswx_hip.h "warp",
+proteus_amd/warp.py makes the mesh) onto the lattice of input 1 -- into a window of the inputs' size around the centre of its
+footprint, so the corners that a rotation of a few degrees turns out of that window are lost -- and then placed like the
+others.  With --bodies FILE.json the water bodies of the LAST canvas are labelled on the GPU
 (include/dswx_hip.h "label") and the summary is written to FILE.json and printed as one line of JSON: a lake on a seam is ONE
 body.  PROTEUS has no such tool: there is no reference output to be equal to; proteus_amd/mosaic.py states what the layers are.
 """
@@ -29,7 +33,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np   # noqa: E402
 
-from proteus_amd import dswx_hls, geotiff, pipeline   # noqa: E402
+from proteus_amd import _capi, dswx_hls, geotiff, pipeline, warp   # noqa: E402
 from proteus_amd.label import wtr_label_spec   # noqa: E402
 from proteus_amd.mosaic import layout, wtr_mosaic_spec   # noqa: E402
 from proteus_amd.stack import MAX_TILES, NONE, NO_SHARE   # noqa: E402
@@ -40,20 +44,81 @@ _spec.loader.exec_module(_stack_tool)
 read_stack = _stack_tool.read_stack
 
 PROJECTION_TAGS = (geotiff.TAG_GEOKEYS, geotiff.TAG_GEO_DOUBLES, geotiff.TAG_GEO_ASCII)
+REPROJECT_SHIFT = 5                     # --reproject: a mesh node every 32 pixels
 
 
-def place_files(infos):
+def same_projection(a, b):
+    for tag in PROJECTION_TAGS:
+        x, y = a.geo_tags.get(tag), b.geo_tags.get(tag)
+        if (x is None) != (y is None) or (x is not None and (x[0] != y[0] or list(x[1]) != list(y[1]))):
+            return False
+    return True
+
+
+def reproject_window(gt, epsg, gt1, epsg1, height, width):
+    """The geotransform of the height x width window on the lattice of input 1 (gt1, epsg1) around the centre of the footprint
+    of an input with geotransform gt and EPSG code epsg (None / equal codes: the same SRS)."""
+    cx, cy = gt[0] + width / 2.0 * gt[1], gt[3] + height / 2.0 * gt[5]
+    if epsg != epsg1:
+        cx, cy = (float(v) for v in warp.utm_to_utm(cx, cy, epsg, epsg1))
+    col0 = int(round((cx - gt1[0]) / gt1[1] - width / 2.0))
+    row0 = int(round((cy - gt1[3]) / gt1[5] - height / 2.0))
+    return (gt1[0] + col0 * gt1[1], gt1[1], 0.0, gt1[3] + row0 * gt1[5], 0.0, gt1[5])
+
+
+def reproject_inputs(engine, plane, infos):
+    """--reproject: every input that is not on the lattice of input 1 -- another WGS 84 / UTM zone, an origin that is not a
+    whole number of pixels away, another pixel size -- is resampled on the device, in its slot of `plane`, onto its
+    reproject_window.  Returns the geotransforms that place the slots and the (1-based) inputs that were resampled."""
+    first = infos[0]
+    gt1 = tuple(float(v) for v in first.geotransform)
+    H, W = first.height, first.width
+    gts, moved = [gt1], []
+    for k, info in enumerate(infos[1:], 2):
+        gt = tuple(float(v) for v in info.geotransform)
+        same = same_projection(first, info)
+        col, row = (gt[0] - gt1[0]) / gt1[1], (gt[3] - gt1[3]) / gt1[5]
+        if same and gt[1:3] == gt1[1:3] and gt[4:] == gt1[4:] and abs(col - round(col)) <= 1e-6 and abs(row - round(row)) <= 1e-6:
+            gts.append(gt)
+            continue
+        epsg, epsg1 = (None, None) if same else (warp.epsg_of(info.geo_tags), warp.epsg_of(first.geo_tags))
+        try:
+            window = reproject_window(gt, epsg, gt1, epsg1, H, W)
+            mesh, _ = warp.mesh_between(gt, epsg, window, epsg1, (H, W), REPROJECT_SHIFT)
+        except ValueError as e:
+            raise ValueError(f'[FAIL] Reprojecting input {k}\n       * {e}.') from None
+        table, tmp = engine.upload(mesh), engine.plane((H, W), np.uint8)
+        try:
+            with engine.lock:
+                slot = plane.ptr + (k - 1) * H * W
+                engine.ctx.warp_device(slot, warp.Spec(1, REPROJECT_SHIFT, dswx_hls.UINT8_FILL_VALUE), 1, H, W, table.ptr, H, W,
+                                       _capi.WarpOut.of(dst=tmp.ptr))
+                engine.ctx.copy_2d_device(slot, H * W, tmp.ptr, H * W, H * W, 1)
+                engine.ctx.synchronize()
+        finally:
+            table.release()
+            tmp.release()
+        gts.append(window)
+        moved.append(k)
+    return gts, moved
+
+
+def place_files(infos, geotransforms=None, moved=()):
     """(canvas_h, canvas_w, place, canvas geotransform, canvas geo tags) of the files; refused: another projection than the
-    first file's, and what proteus_amd.mosaic.layout refuses."""
+    first file's, and what proteus_amd.mosaic.layout refuses.  --reproject gives the geotransforms of the slots and the
+    (1-based) inputs it has resampled, whose own projection no longer matters."""
     first = infos[0]
     for k, info in enumerate(infos):
+        if k + 1 in moved:
+            continue
         for tag in PROJECTION_TAGS:
             a, b = first.geo_tags.get(tag), info.geo_tags.get(tag)
             if (a is None) != (b is None) or (a is not None and (a[0] != b[0] or list(a[1]) != list(b[1]))):
                 raise ValueError(f'[FAIL] Comparing projection\n       * input 1 GeoTIFF tag {tag} with content "{a}" differs from input '
                                  f'{k + 1} GeoTIFF tag {tag} with content "{b}".')
     try:
-        canvas_h, canvas_w, place, gt = layout([tuple(float(v) for v in i.geotransform) for i in infos], first.height, first.width)
+        canvas_h, canvas_w, place, gt = layout(geotransforms if geotransforms is not None else
+                                               [tuple(float(v) for v in i.geotransform) for i in infos], first.height, first.width)
     except ValueError as e:
         raise ValueError(f'[FAIL] Comparing geotransform\n       * {e}.') from None
     tags = dict(first.geo_tags)
@@ -69,6 +134,7 @@ def main(argv=None):
     ap.add_argument('-o', '--output-prefix', dest='prefix', type=str, required=True, help='PREFIX of the five output files')
     ap.add_argument('--band', type=int, default=1, metavar='N', help='band of the product files to mosaic (default 1 = WTR)')
     ap.add_argument('--no-partial', action='store_true', help='partial surface water counts as clear and not water')
+    ap.add_argument('--reproject', action='store_true', help='resample inputs in another UTM zone or off the lattice of input 1 onto it (nearest pixel)')
     ap.add_argument('--bodies', type=str, default=None, metavar='FILE.json', help='label the water bodies of LAST, write the summary')
     ap.add_argument('--device', type=int, default=None, metavar='N', help='GPU to run on (default $DSWX_DEVICE or 0)')
     args = ap.parse_args(argv)
@@ -87,7 +153,8 @@ def main(argv=None):
         print(e)
         return 1
     try:
-        canvas_h, canvas_w, place, gt, tags = place_files(infos)
+        gts, moved = reproject_inputs(engine, plane, infos) if args.reproject else (None, ())
+        canvas_h, canvas_w, place, gt, tags = place_files(infos, gts, moved)
     except ValueError as e:
         plane.release()
         print(e)
@@ -101,6 +168,8 @@ def main(argv=None):
     md['MOSAIC_INPUT_BAND'] = str(args.band)
     md['MOSAIC_PARTIAL_SURFACE_WATER_IS_WATER'] = str(not args.no_partial)
     md['MOSAIC_PLACEMENTS_ROW_COL'] = ', '.join(f'{int(r)} {int(c)}' for r, c in place)
+    if args.reproject:
+        md['MOSAIC_REPROJECTED_INPUTS'] = ', '.join(str(k) for k in moved)
     said = None
     if args.bodies is not None:
         lab = res['last'].label(wtr_label_spec(1, partial_is_water=not args.no_partial), want=('summary',))

@@ -1286,8 +1286,9 @@ int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, c
  * DSWX_STACK_MAX_TILES; n_tiles == 0 writes the outside values; an empty canvas writes nothing; an empty tile raster covers
  * nothing.  canvas_h, canvas_w <= 2^30.  All of it is integer arithmetic per pixel: the result is deterministic and
  * independent of the launch geometry.
- * THE LIMITS THAT REMAIN.  The tiles of one plane share a size, and placement is in whole pixels of ONE lattice: nothing is
- * resampled or reprojected, so a neighbour in another UTM zone is still refused by the tools. */
+ * THE LIMITS THAT REMAIN.  The tiles of one plane share a size, and placement is in whole pixels of ONE lattice: these entries
+ * resample and reproject nothing.  A neighbour in another UTM zone goes through the warp entries below first (bin/dswx_mosaic.py
+ * --reproject); without that it is refused by the tools as before. */
 #define DSWX_HAS_MOSAIC 1
 typedef struct dswx_mosaic_spec {
     int32_t n_cats;                    /* 1 .. DSWX_STACK_MAX_CATS */
@@ -1323,6 +1324,94 @@ int dswx_mosaic_host(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64
                      int64_t tile_stride_elems, const int32_t* place_host, int64_t canvas_h, int64_t canvas_w,
                      const dswx_stack_out_t* out_host);
 
+/* ---- warp: planes resampled onto another lattice through a coordinate mesh, nearest pixel (additive to ABI v7) -------------
+ * Every entry above leaves a pixel where it is or moves it by whole pixels of one lattice.  These entries move the pixels of a
+ * plane to the positions that a MESH of source coordinates names, without the plane crossing PCIe: a neighbour in another UTM
+ * zone onto the lattice of this tile (then dswx_mosaic_*), a product on a shifted or coarser lattice over another one, a
+ * caller's land cover that is not on the HLS grid.  The split is that of dswx_burn_*: coordinates are int32 in 1/256 pixel, the
+ * device sees numbers and never a projection (proteus_amd/warp.py computes meshes for north-up geotransforms and for pairs of
+ * WGS 84 / UTM zones on the host).  A C caller tests for the entries with DSWX_HAS_WARP.
+ * STILL REFUSED: bilinear / cubic resampling of float planes (the DEM's `cubic`); mode or average resampling onto coarser
+ * lattices (dswx_grid_* aggregates); SRSs other than WGS 84 / UTM; antimeridian handling; reading .shp.
+ * UNPINNED: GDAL and PROJ are not part of this project's environment, so gdal.Warp's own choice of the nearest pixel, its
+ * approximate transformer (0.125 pixel error threshold) and its handling of a centre exactly on a pixel boundary are not
+ * pinned by any test.  The definition below is this project's own.
+ * THE DEFINITION.
+ *   SOURCE     a plane [n_tiles][src_tile_stride] of elements of elem_bytes in {1, 2, 4} (class planes, int16 bands, DIAG,
+ *              uint32 label / dense / acc planes, float32 planes as bit patterns): elements are copied, never interpreted.
+ *              Every tile is a raster of height x width with row pitch `width`; the padding up to the stride is never read;
+ *              stride 0 = height * width.
+ *   DST        dst_h x dst_w per tile, dense.
+ *   MESH       int32 [mesh_h][mesh_w][2] = (x, y) in 1/256 SOURCE pixel, x right and y down as for the burn entries: source
+ *              pixel (c, r) has its centre at (256 c + 128, 256 r + 128).  step = 1 << shift, shift 0 .. 8; mesh_h = ((dst_h +
+ *              step - 1) >> shift) + 1, mesh_w likewise.  Node (i, j) is the source position of the CENTRE of destination pixel
+ *              (X, Y) = (j * step, i * step), which may lie past the destination's edge.  mesh_tile_stride_nodes 0 = one mesh
+ *              for all tiles (the dates of one MGRS tile), else the nodes between the meshes of consecutive tiles.  ANY
+ *              CONTENT IS LEGAL: INT32_MIN and INT32_MAX are ordinary values, garbage maps to garbage positions.
+ *   POSITION   of destination pixel (X, Y): i = Y >> shift, fy = Y & (step - 1), j = X >> shift, fx = X & (step - 1); in
+ *              64-bit integers, for x and in the same way for y,
+ *                  num = (step - fy) * ((step - fx) * x[i][j]     + fx * x[i][j + 1])
+ *                      +  fy         * ((step - fx) * x[i + 1][j] + fx * x[i + 1][j + 1])
+ *                  sx  = (num + (1 << (2 * shift - 1))) >> (2 * shift)      (arithmetic shift; shift == 0: sx = x[i][j])
+ *              |num| < 2^48.  The nearest source pixel is c = sx >> 8, r = sy >> 8 (floor); it is INSIDE iff 0 <= c < width and
+ *              0 <= r < height.
+ *   dst        [n_tiles][dst_h * dst_w] elements: the element of source pixel (c, r) of the same tile where inside, else the
+ *              low elem_bytes bytes of spec.outside.  NULL = not wanted.
+ *   src_index  uint32 [n_tiles][dst_h * dst_w]: r * width + c where inside, else DSWX_WARP_OUTSIDE (0xFFFFFFFF): a caller
+ *              warps further planes by a plain gather, and a label plane stays meaningful.  NULL = not wanted.
+ *   head       uint64 [n_tiles][DSWX_WARP_HEAD_WORDS]: word 0 the destination pixels, 1 those inside, 2 those outside, 3 and 4
+ *              the smallest and the largest source row used (height and 0 if none), 5 and 6 the same for columns (width and
+ *              0), 7 zero.  NULL = not wanted.
+ * height * width <= 2^30 and dst_h * dst_w <= 2^30 (so every side is <= 2^30).  n_tiles == 0 or an empty destination writes
+ * nothing; an empty source raster makes every pixel outside.  All of it is integer arithmetic per pixel: the result is
+ * deterministic and independent of the launch geometry; no atomics touch the planes, and the atomics of `head` (add, min,
+ * max) commute. */
+#define DSWX_HAS_WARP 1
+#define DSWX_WARP_HEAD_WORDS 8
+#define DSWX_WARP_MAX_SHIFT 8
+#define DSWX_WARP_OUTSIDE 0xFFFFFFFFu
+typedef struct dswx_warp_spec {
+    int32_t  elem_bytes;               /* 1, 2 or 4 */
+    int32_t  shift;                    /* 0 .. DSWX_WARP_MAX_SHIFT: a mesh node every 1 << shift destination pixels */
+    uint32_t outside;                  /* its low elem_bytes bytes are the element of a pixel that is not inside */
+    int32_t  reserved;                 /* must be 0 */
+    int64_t  src_tile_stride;          /* elements between the tiles of the plane; 0 = height * width */
+    int64_t  mesh_tile_stride_nodes;   /* nodes between the meshes of consecutive tiles; 0 = one mesh for all tiles */
+} dswx_warp_spec_t;                    /* 32 bytes */
+typedef struct dswx_warp_out {
+    void*     dst;                     /* [n_tiles][dst_h * dst_w] elements of elem_bytes; NULL = not wanted */
+    uint32_t* src_index;               /* [n_tiles][dst_h * dst_w]; NULL = not wanted */
+    uint64_t* head;                    /* [n_tiles][8]; NULL = not wanted */
+} dswx_warp_out_t;
+/* One plane in DEVICE memory, warped through mesh_device (DEVICE memory, read by the device only) -> the wanted outputs of
+ * *out_device (device memory).  Asynchronous on `stream` (NULL = the context's stream): one hipMemsetAsync of `head` (only if
+ * wanted) and ONE kernel launch, whatever the tile count (past the 65535 tiles of grid.y the workgroups walk the tiles); no
+ * synchronisation, no scratch of the context, no allocation, and nothing the caller has to zero in front: a second call on
+ * the same outputs gives the same bytes.  No workgroup ever waits for another.  A NULL spec or out struct, elem_bytes not 1 /
+ * 2 / 4, shift outside 0 .. 8, reserved != 0, a negative size, tile count or stride, a stride that is neither 0 nor large
+ * enough (src: height * width, mesh: mesh_h * mesh_w), height * width or dst_h * dst_w above 2^30, more than 2^32 tiles or a
+ * plane above 2^46 elements, a NULL mesh or a NULL plane (of rasters that are not empty) with something to write:
+ * DSWX_ERR_ARG; mesh or src_index off 4 bytes, head off 8, plane or dst off elem_bytes: DSWX_ERR_ALIGN.  (The arguments are
+ * checked before the context is, and a refused call writes nothing.)  Every output NULL is no work, not an error.  Overlap of
+ * the outputs with the plane, the mesh or each other is NOT CHECKED. */
+int dswx_warp_device(dswx_ctx_t* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height,
+                     int64_t width, const int32_t* mesh_device, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out_device,
+                     void* stream);
+/* Plane `plane` of a resident batch -- ANY DSWX_PLANE_* but DSWX_PLANE_COUNTERS: the bands, Fmask, the masks, DIAG, every
+ * layer -- tiles tile0 .. tile0 + n_tiles - 1 (n_tiles DSWX_BATCH_ALL_TILES = up to the last), warped through mesh_device,
+ * whose mesh 0 belongs to tile0 -> the wanted outputs of *out_device: the caller's device memory, tile 0 = tile0.  The element
+ * size is the plane table's: a spec->elem_bytes that disagrees is DSWX_ERR_ARG, and so is a spec->src_tile_stride that is not 0
+ * (the plane has the stride of the batch).  Asynchronous on `stream` (NULL = the stream of the batch's context) like
+ * dswx_warp_device.  A plane the batch does not have or DSWX_PLANE_COUNTERS: DSWX_ERR_ARG, and dswx_last_error() names the
+ * plane.  Tile ranges: the rules of dswx_batch_compare. */
+int dswx_batch_warp(dswx_batch_t* batch, int32_t plane, const dswx_warp_spec_t* spec, int64_t tile0, int64_t n_tiles,
+                    const int32_t* mesh_device, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++, with a HOST mesh: needs no device and no context.  The other half of
+ * a comparison, not a fallback of the two entries above.  The refusals of dswx_warp_device, except that every buffer may sit
+ * at any address. */
+int dswx_warp_host(const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                   const int32_t* mesh_host, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1351,7 +1440,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* / dswx_*warp* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

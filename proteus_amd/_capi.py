@@ -49,7 +49,8 @@ EXPORTED_SYMBOLS = (
     'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host',
     'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host',
     'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host',
-    'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host')
+    'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host',
+    'dswx_warp_device', 'dswx_batch_warp', 'dswx_warp_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -85,6 +86,11 @@ HAS_MOSAIC = 1                    # DSWX_HAS_MOSAIC: additive to ABI v7
 # in LDS, the placements tested per step and the loads in flight per thread (tests build shapes around the seams)
 MOSAIC_RECT_H, MOSAIC_RECT_W, MOSAIC_LIST, MOSAIC_CHUNK, MOSAIC_ROUND = 4, 1024, 512, 256, 8
 MOSAIC_MAX_SIDE = 1 << 30
+HAS_WARP = 1                      # DSWX_HAS_WARP: additive to ABI v7
+WARP_HEAD_WORDS, WARP_MAX_SHIFT, WARP_OUTSIDE, WARP_MAX_PIXELS = 8, 8, 0xFFFFFFFF, 1 << 30
+# csrc/dswx_warp.hip: the rows and the columns of the destination rectangle of one workgroup, the pixels of a thread, and the
+# shift below which a thread's pixels cross mesh cells (tests build shapes around the seams)
+WARP_RECT_H, WARP_RECT_W, WARP_UNIT, WARP_FINE_BELOW = 4, 1024, 16, 4
 
 
 class DswxError(RuntimeError):
@@ -213,6 +219,26 @@ class MosaicSpec(ctypes.Structure):
         c = cls(spec.n_cats, spec.fill, spec.outside, getattr(spec, 'reserved', 0))
         ctypes.memmove(c.cat_of_byte, spec.cat_of_byte.ctypes.data, 256)
         return c
+
+
+class WarpSpec(ctypes.Structure):
+    """dswx_warp_spec_t; proteus_amd.warp.Spec is the Python form."""
+    _fields_ = [('elem_bytes', ctypes.c_int32), ('shift', ctypes.c_int32), ('outside', ctypes.c_uint32), ('reserved', ctypes.c_int32),
+                ('src_tile_stride', ctypes.c_int64), ('mesh_tile_stride_nodes', ctypes.c_int64)]
+
+    @classmethod
+    def of(cls, spec):
+        return cls(int(spec.elem_bytes), int(spec.shift), int(spec.outside) & 0xFFFFFFFF, int(getattr(spec, 'reserved', 0)),
+                   int(spec.src_tile_stride), int(spec.mesh_tile_stride_nodes))
+
+
+class WarpOut(ctypes.Structure):
+    """dswx_warp_out_t: addresses, 0 / None = not wanted."""
+    _fields_ = [('dst', ctypes.c_void_p), ('src_index', ctypes.c_void_p), ('head', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, dst=None, src_index=None, head=None):
+        return cls(dst or None, src_index or None, head or None)
 
 
 class GridSpec(ctypes.Structure):
@@ -522,6 +548,9 @@ def load_library(path=None):
         'dswx_mosaic_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, i64, i64, vp, vp]),
         'dswx_batch_mosaic': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, i64, i64, vp, vp]),
         'dswx_mosaic_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp, i64, i64, vp]),
+        'dswx_warp_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp]),
+        'dswx_batch_warp': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, i64, i64, vp, vp]),
+        'dswx_warp_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
         'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
@@ -1173,6 +1202,15 @@ class Context:
                                            int(height), int(width), int(tile_stride), ctypes.c_void_p(place_ptr), int(canvas_h),
                                            int(canvas_w), ctypes.byref(out), _stream_arg(stream)))
 
+    def warp_device(self, plane_ptr, spec, n_tiles, height, width, mesh_ptr, dst_h, dst_w, out, stream=None):
+        """dswx_warp_device: one device plane [n_tiles][spec.src_tile_stride] of elements of spec.elem_bytes, every tile a height
+        x width raster, resampled (nearest pixel) onto dst_h x dst_w through the device mesh int32 [mesh_h][mesh_w][2] at
+        mesh_ptr (a warp.Spec; include/dswx_hip.h "warp", proteus_amd/warp.py states the definition in numpy) -> the outputs
+        `out` names (a WarpOut of device addresses); one memset of the head and one launch, asynchronous."""
+        _check(self.lib.dswx_warp_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(WarpSpec.of(spec)), int(n_tiles),
+                                         int(height), int(width), ctypes.c_void_p(mesh_ptr), int(dst_h), int(dst_w),
+                                         ctypes.byref(out), _stream_arg(stream)))
+
     def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
         onto cells by `spec` (a grid.Spec; include/dswx_hip.h "grid", proteus_amd/grid.py states the definition in numpy) ->
@@ -1395,6 +1433,35 @@ def mosaic_host(tiles, place, canvas_shape, spec, want=('count', 'last', 'last_i
                       **{k: res[k].ctypes.data for k in ('last', 'last_index', 'share') if k in res})
     _check(load_library().dswx_mosaic_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(MosaicSpec.of(spec)), n, H, W,
                                            stride, _host_ptr(place) if n else None, ch, cw, ctypes.byref(out)))
+    return res
+
+
+def _warp_planes(want, elem_dtype, n, dst_shape, make):
+    """{name: plane} for the outputs of a warp named in `want`, each made by make(shape, dtype)."""
+    dh, dw = (max(int(v), 0) for v in dst_shape)
+    shapes = {'dst': ((n, dh, dw), elem_dtype), 'src_index': ((n, dh, dw), np.uint32), 'head': ((n, WARP_HEAD_WORDS), np.uint64)}
+    want = _wanted(want, shapes)
+    return {k: make(*shapes[k]) for k in shapes if k in want}
+
+
+def warp_host(tiles, mesh, spec, dst_shape, want=('dst', 'src_index', 'head'), raster=None):
+    """dswx_warp_host (no device needed): the outputs of proteus_amd.warp.warp_tiles named in `want` -- 'dst' [n, dst_h, dst_w]
+    of the plane's dtype, 'src_index' uint32 [n, dst_h, dst_w], 'head' uint64 [n, 8] -- of a host plane [n_tiles, H, W] of 1, 2
+    or 4 bytes per element warped through the int32 mesh `mesh` ([mesh_h, mesh_w, 2], or per tile at
+    spec.mesh_tile_stride_nodes) by `spec` (a warp.Spec), by the library's scalar statement of the definition.  With
+    raster=(H, W), `tiles` is a padded plane [n_tiles, spec.src_tile_stride] whose padding is not read."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype.itemsize != spec.elem_bytes or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride] of {spec.elem_bytes}-byte elements, '
+                         f'not {tiles.dtype} {tiles.shape}')
+    n = tiles.shape[0]
+    H, W = tiles.shape[1:] if raster is None else raster
+    mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+    dh, dw = (int(v) for v in dst_shape)
+    res = _warp_planes(want, tiles.dtype, n, (dh, dw), lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = WarpOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_warp_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(WarpSpec.of(spec)), n, int(H), int(W),
+                                         _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
     return res
 
 
@@ -1872,6 +1939,24 @@ class DeviceBatch:
             _check(self.ctx.lib.dswx_batch_mosaic(self.handle, plane, ctypes.byref(MosaicSpec.of(spec)), int(tile0),
                                                   self._tiles(tile0, n_tiles)[0], ctypes.c_void_p(place_ptr), ch, cw,
                                                   ctypes.byref(out), _stream_arg(stream)))
+        return res
+
+    def warp(self, name, mesh_ptr, dst_shape, spec, tile0=0, n_tiles=None, want=('dst', 'src_index', 'head'), stream=None):
+        """dswx_batch_warp: tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of ANY plane `name` but the
+        counters resampled (nearest pixel) onto dst_shape = (dst_h, dst_w) through the DEVICE mesh int32 [mesh_h][mesh_w][2] at
+        mesh_ptr (mesh 0 belongs to tile0) by `spec` (a warp.Spec whose elem_bytes is the plane's), by one memset and ONE kernel
+        launch, asynchronous on `stream`.  Returns {output: DeviceBuffer} for the outputs named in `want`: 'dst' [n_tiles][dst_h *
+        dst_w] elements, 'src_index' uint32 of the same shape, 'head' uint64 [n_tiles][8] -- device memory owned by the caller.
+        proteus_amd.warp.warp_tiles of the downloaded tiles gives the same arrays."""
+        plane = _plane_index(name)
+        n_tiles, nt = self._tiles(tile0, n_tiles)
+        elem = {1: np.uint8, 2: np.uint16, 4: np.uint32}.get(int(spec.elem_bytes), np.uint8)
+        res = _malloc_planes(self.ctx, _warp_planes(want, elem, nt, dst_shape, lambda shp, dt: (shp, dt)))
+        out = WarpOut.of(**{k: b.ptr for k, b in res.items()})
+        with _owned(res):
+            _check(self.ctx.lib.dswx_batch_warp(self.handle, plane, ctypes.byref(WarpSpec.of(spec)), int(tile0), n_tiles,
+                                                ctypes.c_void_p(mesh_ptr), int(dst_shape[0]), int(dst_shape[1]), ctypes.byref(out),
+                                                _stream_arg(stream)))
         return res
 
     def grid(self, name, spec, tile0=0, n_tiles=None, want=('count', 'share', 'coverage', 'major'), stream=None):

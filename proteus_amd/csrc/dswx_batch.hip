@@ -558,6 +558,31 @@ int dswx_batch_mosaic(dswx_batch_t* b, int32_t plane, const dswx_mosaic_spec_t* 
                               dswx_stream_of(ctx, stream));
 }
 
+// The tiles of ANY plane of a resident batch but the counters warped through a mesh of source coordinates (dswx_warp.hip), one
+// memset and one launch, asynchronous: the mesh and the outputs are the caller's device memory, so nothing is allocated, copied
+// or waited for here.  The element size is the plane table's; mesh 0 belongs to tile0.
+int dswx_batch_warp(dswx_batch_t* b, int32_t plane, const dswx_warp_spec_t* spec, int64_t tile0, int64_t n_tiles, const int32_t* mesh,
+                    int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, void* stream) {
+    if (!b) return dswx_fail(DSWX_ERR_ARG, "batch is NULL");
+    if (plane < 0 || plane >= DSWX_BATCH_MAX_PLANES) return dswx_fail(DSWX_ERR_ARG, "plane %d: not 0 .. %d", plane, DSWX_BATCH_MAX_PLANES - 1);
+    if (plane == DSWX_PLANE_COUNTERS)
+        return dswx_fail(DSWX_ERR_ARG, "the counters are not warped (three int64 per tile): read them (dswx_batch_planes)");
+    const dswx_batch_view v = view_of(b);
+    const dswx_plane_desc& d = DSWX_PLANES[plane];
+    if (!v.ptr[plane]) return dswx_fail(DSWX_ERR_ARG, "the batch has no plane %d (%s)", plane, d.name);
+    if (spec && spec->elem_bytes != d.bytes)
+        return dswx_fail(DSWX_ERR_ARG, "elem_bytes %d, but plane %d (%s) has %d bytes per pixel", spec->elem_bytes, plane, d.name, d.bytes);
+    if (spec && spec->src_tile_stride)
+        return dswx_fail(DSWX_ERR_ARG, "src_tile_stride %lld must be 0: the plane has the stride of the batch", (long long)spec->src_tile_stride);
+    if (int rc = dswx_select_tiles({&v}, tile0, &n_tiles, "the batch")) return rc;
+    const char* base = dswx_select_base(v, plane, tile0);
+    int64_t stride;
+    if (int rc = dswx_warp_check(base, spec, n_tiles, v.height, v.width, mesh, dst_h, dst_w, out, &stride, true)) return rc;
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return dswx_warp_launch(ctx, base, spec, n_tiles, v.height, v.width, v.tile_stride, mesh, dst_h, dst_w, out, dswx_stream_of(ctx, stream));
+}
+
 // `launches` launches of the real kernel over the whole batch, after one untimed launch; ms per launch
 static int probe_ms(dswx_batch* b, const dswx_params_t* params, int launches, hipEvent_t e0, hipEvent_t e1, float* ms) {
     hipStream_t s = b->ctx->stream;

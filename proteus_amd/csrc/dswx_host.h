@@ -314,6 +314,14 @@ int dswx_mosaic_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_mosaic_sp
                        int64_t width, int64_t stride, const int32_t* place, int64_t canvas_h, int64_t canvas_w,
                        const dswx_stack_out_t* out, hipStream_t s);
 
+// ---- warp (dswx_warp.hip): the shared checks of the entries (resolves the stride of the plane, 0 = height * width; `align`:
+// mesh and src_index must be 4-byte, head 8-byte and plane and dst elem_bytes aligned), and the memset and the launch for
+// arguments that passed them, with the stride of the plane given apart from the spec (a batch has its own)
+int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                    const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, int64_t* src_stride, bool align);
+int dswx_warp_launch(dswx_ctx* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                     int64_t src_stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, hipStream_t s);
+
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,
                              size_t info_len);

@@ -153,6 +153,40 @@ class DevicePlane:
         res.update(made)
         return res
 
+    def warp(self, mesh, dst_shape, shift, outside=0, want=('dst',)):
+        """The rasters of a [n, H, W] (or one [H, W]) plane of 1-, 2- or 4-byte elements resampled (nearest pixel) onto
+        dst_shape = (dst_h, dst_w) through `mesh` as they lie in HBM (dswx_warp_device; proteus_amd.warp.warp_tiles of the same
+        arrays gives the same arrays): int32 [mesh_h, mesh_w, 2] for all rasters or [n, mesh_h, mesh_w, 2], in 1/256 source
+        pixel, a node every 1 << shift destination pixels (warp.affine_mesh and warp.utm_mesh make one from geotransforms).
+        A dict of DevicePlanes for the outputs named in `want` -- 'dst' [n, dst_h, dst_w] of this plane's dtype ([dst_h, dst_w]
+        for one raster), 'src_index' uint32 of the same shape, 'head' uint64 [n, 8] -- which stay on the device: 'dst' of a
+        neighbour in another UTM zone can be mosaicked, labelled or written."""
+        from . import warp as _warp
+        if len(self.shape) not in (2, 3) or self.dtype.itemsize not in (1, 2, 4):
+            raise ValueError(f'a warp is made of a [n, H, W] or [H, W] plane of 1-, 2- or 4-byte elements, not {self.dtype} {self.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        shape = tuple(int(v) for v in dst_shape)
+        if len(shape) != 2 or min(shape) < 0 or shape[0] * shape[1] > _capi.WARP_MAX_PIXELS:
+            raise ValueError(f'a destination is (dst_h, dst_w) of at most {_capi.WARP_MAX_PIXELS} pixels, not {dst_shape}')
+        mh, mw = _warp.mesh_shape(shape, shift)
+        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+        if mesh.shape not in ((mh, mw, 2), (n_tiles, mh, mw, 2)):
+            raise ValueError(f'a mesh for {shape} at shift {shift} is [{mh}, {mw}, 2] or [{n_tiles}, {mh}, {mw}, 2], not {mesh.shape}')
+        spec = _warp.Spec(self.dtype.itemsize, shift, outside, mesh_tile_stride_nodes=mh * mw if mesh.ndim == 4 else 0)
+        lead = (n_tiles,) if len(self.shape) == 3 else ()
+        made = _capi._warp_planes(want, self.dtype, n_tiles, shape,
+                                  lambda shp, dt: self.engine.plane(shp if len(shp) == 2 else lead + tuple(shp[1:]), dt))
+        out = _capi.WarpOut.of(**{k: p.ptr for k, p in made.items()})
+        table = self.engine.upload(mesh)
+        try:
+            with self.engine.lock, stages.span('gpu: warp'):
+                self.engine.ctx.warp_device(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
+                self.engine.ctx.synchronize()
+        finally:
+            table.release()
+        return made
+
     def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
         """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;
         proteus_amd.grid.grid_tiles of the same array gives the same planes): a dict of [n, GH, GW] DevicePlanes for the
