@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`dswx_warp.py product.tif --like other.tif [--band N] [--shift 6] [--outside 255] [--device N] -o out.tif`
+"""`dswx_warp.py product.tif --like other.tif [--band N] [--shift 6] [--outside 255] [--resample nearest] [--device N] -o out.tif`
 
 One layer laid over the lattice of another file on the GPU (include/dswx_hip.h "warp"): band N (default 1) of product.tif is
 read into HBM, a mesh of source coordinates is computed on the host from the two geotransforms and GeoKeys -- the same SRS
@@ -10,8 +10,11 @@ product get --outside (default 255, the product's fill).  out.tif is a COG with 
 other.tif and the metadata of product.tif.  One line of JSON says how many pixels were inside and how far the interpolated
 mesh is from the exact mapping at most (in 1/256 pixel of the product): choose a smaller --shift if that is too far.
 
-Nearest pixel only: no bilinear / cubic / mode / average resampling; no SRS other than WGS 84 / UTM across files; no
-antimeridian.  PROTEUS does this through gdal.Warp, which is not part of this project's environment: GDAL's own choice of the
+--resample bilinear | cubic INTERPOLATES a float32 or int16 band instead (include/dswx_hip.h "resample"): the input's nodata
+value marks taps that are not valid, and --outside is the value of the pixels without a valid tap.  The input may then be in
+EPSG:4326 under a WGS 84 / UTM lattice (proteus_amd.warp.geographic_mesh).  The default, nearest, is the path described above, and refuses such an input as before.
+
+No mode / average resampling; no SRS other than EPSG:4326 and WGS 84 / UTM across files; no antimeridian.  PROTEUS does this through gdal.Warp, which is not part of this project's environment: GDAL's own choice of the
 nearest pixel, its approximate transformer (0.125 pixel error threshold) and its handling of a centre exactly on a pixel
 boundary are not pinned by execution; proteus_amd/warp.py states what this tool computes.
 """
@@ -23,7 +26,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np   # noqa: E402
 
-from proteus_amd import dswx_hls, geotiff, pipeline, warp   # noqa: E402
+from proteus_amd import dswx_hls, geotiff, pipeline, resample, warp   # noqa: E402
 
 PROJECTION_TAGS = (geotiff.TAG_GEOKEYS, geotiff.TAG_GEO_DOUBLES, geotiff.TAG_GEO_ASCII)
 
@@ -55,13 +58,17 @@ def same_projection(a, b):
     return True
 
 
-def mesh_for(src_info, dst_info, shift):
-    """(mesh, deviation in 1/256 source pixel) that lays src_info's raster onto dst_info's lattice."""
+def mesh_for(src_info, dst_info, shift, geographic=False):
+    """(mesh, deviation in 1/256 source pixel) that lays src_info's raster onto dst_info's lattice; `geographic`: a source in
+    EPSG:4326 is taken (the interpolating methods), not refused (nearest, as before)."""
     src_gt, dst_gt = (tuple(float(v) for v in i.geotransform) for i in (src_info, dst_info))
     shape = (dst_info.height, dst_info.width)
     if same_projection(src_info, dst_info):
         return warp.affine_mesh(src_gt, dst_gt, shape, shift), 0.0
-    return warp.utm_mesh(src_gt, warp.epsg_of(src_info.geo_tags), dst_gt, warp.epsg_of(dst_info.geo_tags), shape, shift)
+    src_epsg, dst_epsg = warp.epsg_of(src_info.geo_tags), warp.epsg_of(dst_info.geo_tags)
+    if geographic and src_epsg == warp.GEOGRAPHIC_EPSG:
+        return warp.geographic_mesh(src_gt, dst_gt, dst_epsg, shape, shift)
+    return warp.utm_mesh(src_gt, src_epsg, dst_gt, dst_epsg, shape, shift)
 
 
 def main(argv=None):
@@ -72,6 +79,8 @@ def main(argv=None):
     ap.add_argument('--band', type=int, default=1, metavar='N', help='band of the input file (default 1)')
     ap.add_argument('--shift', type=int, default=6, metavar='S', help='a mesh node every 1 << S output pixels, 0 .. 8 (default 6)')
     ap.add_argument('--outside', type=int, default=dswx_hls.UINT8_FILL_VALUE, metavar='V', help='value of the pixels outside the input (default 255)')
+    ap.add_argument('--resample', choices=('nearest', 'bilinear', 'cubic'), default='nearest',
+                    help='nearest (default) copies the nearest pixel; bilinear and cubic interpolate a float32 or int16 band')
     ap.add_argument('--device', type=int, default=None, metavar='N', help='GPU to run on (default $DSWX_DEVICE or 0)')
     args = ap.parse_args(argv)
     for f in (args.input_file, args.like):
@@ -93,12 +102,21 @@ def main(argv=None):
         print(e)
         return 1
     try:
-        mesh, deviation = mesh_for(info, like, args.shift)
+        mesh, deviation = mesh_for(info, like, args.shift, geographic=args.resample != 'nearest')
     except ValueError as e:
         plane.release()
         print(f'ERROR {e}')
         return 1
-    res = plane.warp(mesh, (like.height, like.width), args.shift, outside=args.outside, want=('dst', 'head'))
+    if args.resample != 'nearest':
+        try:
+            word = resample.outside_word(args.outside, plane.dtype) if plane.dtype in resample.DTYPES.values() else 0
+            res = plane.resample(mesh, (like.height, like.width), args.shift, args.resample, nodata=info.nodata, outside=word, want=('dst', 'head'))
+        except ValueError as e:
+            plane.release()
+            print(f'ERROR {e}')
+            return 1
+    else:
+        res = plane.warp(mesh, (like.height, like.width), args.shift, outside=args.outside, want=('dst', 'head'))
     plane.release()
     head = [int(v) for v in res['head'].numpy()[0]]
     res['head'].release()
@@ -107,6 +125,8 @@ def main(argv=None):
     md['WARP_INPUT_BAND'] = str(args.band)
     md['WARP_LIKE_FILE'] = os.path.basename(args.like)
     md['WARP_MESH_SHIFT'] = str(args.shift)
+    if args.resample != 'nearest':
+        md['WARP_RESAMPLE'] = args.resample
     tags = dict(like.geo_tags)
     written = []
     dswx_hls._save_array(res['dst'], args.output, md, tags, output_files_list=written,
@@ -114,6 +134,10 @@ def main(argv=None):
     res['dst'].release()
     for f in written:
         print(f'file saved: {f}')
+    if args.resample != 'nearest':
+        print(json.dumps({'pixels': head[0], 'cubic': head[1], 'bilinear': head[2], 'renormalised': head[3], 'outside': head[4],
+                          'source_rows': head[5:7], 'resample': args.resample, 'mesh_shift': args.shift, 'mesh_deviation_256ths': deviation}))
+        return 0
     print(json.dumps({'pixels': head[0], 'inside': head[1], 'outside': head[2], 'source_rows': head[3:5], 'source_columns': head[5:7],
                       'mesh_shift': args.shift, 'mesh_deviation_256ths': deviation}))
     return 0

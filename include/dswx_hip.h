@@ -1331,8 +1331,9 @@ int dswx_mosaic_host(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64
  * caller's land cover that is not on the HLS grid.  The split is that of dswx_burn_*: coordinates are int32 in 1/256 pixel, the
  * device sees numbers and never a projection (proteus_amd/warp.py computes meshes for north-up geotransforms and for pairs of
  * WGS 84 / UTM zones on the host).  A C caller tests for the entries with DSWX_HAS_WARP.
- * STILL REFUSED: bilinear / cubic resampling of float planes (the DEM's `cubic`); mode or average resampling onto coarser
- * lattices (dswx_grid_* aggregates); SRSs other than WGS 84 / UTM; antimeridian handling; reading .shp.
+ * Bilinear / cubic resampling of float32 and int16 planes (the DEM's `cubic`) is the "resample" section below.
+ * STILL REFUSED: mode or average resampling onto coarser lattices (dswx_grid_* aggregates); SRSs other than EPSG:4326 and
+ * WGS 84 / UTM; antimeridian handling; reading .shp.
  * UNPINNED: GDAL and PROJ are not part of this project's environment, so gdal.Warp's own choice of the nearest pixel, its
  * approximate transformer (0.125 pixel error threshold) and its handling of a centre exactly on a pixel boundary are not
  * pinned by any test.  The definition below is this project's own.
@@ -1412,6 +1413,91 @@ int dswx_batch_warp(dswx_batch_t* batch, int32_t plane, const dswx_warp_spec_t* 
 int dswx_warp_host(const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                    const int32_t* mesh_host, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out_host);
 
+/* ---- resample: float32 and int16 planes interpolated through the coordinate mesh, bilinear and cubic (additive to ABI v7) ---
+ * The entries above copy the NEAREST pixel.  These INTERPOLATE: the DEM, which the reference warps with GDAL's `cubic` for
+ * every product that has one, or an int16 band.  Byte class planes have no business here.  A C caller tests for the entries
+ * with DSWX_HAS_RESAMPLE.
+ * STILL REFUSED: element kinds other than float32 and int16; mode, average or lanczos resampling; a projection on the device.
+ * UNPINNED: GDAL is not part of this project's environment, so gdal.Warp's double-precision positions (ours are quantised to
+ * 1/256 source pixel), its weighting at the raster's border and at nodata taps, and its rounding of integer results are not
+ * pinned by execution.  The definition below is this project's own.
+ * THE DEFINITION.
+ *   SOURCE, DST, MESH and the POSITION (sx, sy) of a destination pixel are EXACTLY those of the section above, in the same
+ *              64-bit integers; the same size limits hold and any mesh content is legal.
+ *   KIND       DSWX_RESAMPLE_F32 (float32) or DSWX_RESAMPLE_I16 (int16).
+ *   METHOD     DSWX_RESAMPLE_BILINEAR or DSWX_RESAMPLE_CUBIC (nearest stays with dswx_warp_*).
+ *   BASE       ux = sx - 128, c0 = ux >> 8, fx = ux & 255, and uy, r0, fy likewise (arithmetic shifts in 64 bits): a sample at
+ *              a pixel centre has f = 0.
+ *   VALID TAP  source pixel (c, r) is valid iff 0 <= c < width and 0 <= r < height (compared in 64 bits BEFORE the load), its
+ *              value is finite (float32 NaN and +-Inf are not) and, if spec.has_nodata, it is != the nodata value: float32
+ *              compared as a value with the float32 whose bits spec.nodata holds, int16 as an integer with (int32_t)
+ *              spec.nodata.  A tap's value is converted to double, exactly.
+ *   WEIGHTS    Keys' cubic with a = -0.5 (Catmull-Rom, GDAL's `cubic`) as INTEGERS over 2^25, f = 0 .. 255:
+ *                  N0 = -65536 f + 512 f^2 - f^3          N1 = 2^25 - 1280 f^2 + 3 f^3
+ *                  N2 =  65536 f + 1024 f^2 - 3 f^3       N3 = -256 f^2 + f^3
+ *              They sum to 2^25, |N| <= 2^25 (exact in a double), and reproduce every polynomial of degree <= 2.
+ *   CUBIC      if all 16 taps (c0 - 1 .. c0 + 2) x (r0 - 1 .. r0 + 2) are valid, with p[r][k] the tap of row r0 - 1 + r and
+ *              column c0 - 1 + k:
+ *                  h_r = ((Nx0 * p[r][0] + Nx1 * p[r][1]) + Nx2 * p[r][2]) + Nx3 * p[r][3]
+ *                  v   = ((Ny0 * h_0 + Ny1 * h_1) + Ny2 * h_2) + Ny3 * h_3            result = v * 2^-50
+ *              every product and every sum ONE IEEE double operation rounded on its own (no fused multiply-add).  Otherwise
+ *              the pixel takes the BILINEAR rule, as GDAL does at borders and masked taps.
+ *   BILINEAR   taps (c0, r0), (c0 + 1, r0), (c0, r0 + 1), (c0 + 1, r0 + 1) in that order with the integer weights
+ *              (256 - fx)(256 - fy), fx (256 - fy), (256 - fx) fy, fx fy.  From S = 0.0 and Wt = 0, over the VALID taps only,
+ *              in that order: S = S + w * p (the product is exact, the sum rounded), Wt += w.  Wt == 0: the pixel is OUTSIDE.
+ *              Wt == 65536: result = S * 2^-16.  Otherwise result = S / (double)Wt.
+ *   ELEMENT    float32: the double rounded to float32, to nearest even; float32 subnormals are kept, a cubic overshoot past
+ *              FLT_MAX becomes an infinity.  int16: rint (half to even), then clamped to -32768 .. 32767.  An OUTSIDE pixel
+ *              gets the low bytes of spec.outside, as in the warp spec.  No NaN is ever produced by arithmetic, so device and
+ *              host agree on every bit.
+ *   dst        [n_tiles][dst_h * dst_w] elements.  NULL = not wanted.
+ *   how        uint8 [n_tiles][dst_h * dst_w]: 0 = outside, 1 = bilinear with all four taps valid, 2 = bilinear with fewer
+ *              (renormalised by Wt), 3 = cubic.  NULL = not wanted.
+ *   head       uint64 [n_tiles][DSWX_RESAMPLE_HEAD_WORDS]: word 0 the destination pixels, 1 those of how 3, 2 of how 1, 3 of
+ *              how 2, 4 of how 0; 5 and 6 the smallest and the largest source ROW among the valid taps of the window used
+ *              (4 x 4 for a cubic pixel, 2 x 2 for a bilinear one, nothing for an outside one; height and 0 if none); 7 zero.
+ *              Column ranges are not reported: a host computes its source window from the mesh.  NULL = not wanted.
+ * There is NO dswx_batch_resample: no plane of a batch is float32, and interpolating class planes is meaningless. */
+#define DSWX_HAS_RESAMPLE 1
+#define DSWX_RESAMPLE_HEAD_WORDS 8
+#define DSWX_RESAMPLE_F32 0
+#define DSWX_RESAMPLE_I16 1
+#define DSWX_RESAMPLE_BILINEAR 1
+#define DSWX_RESAMPLE_CUBIC 2
+typedef struct dswx_resample_spec {
+    int32_t  kind;                     /* DSWX_RESAMPLE_F32 or DSWX_RESAMPLE_I16 */
+    int32_t  method;                   /* DSWX_RESAMPLE_BILINEAR or DSWX_RESAMPLE_CUBIC */
+    int32_t  shift;                    /* 0 .. DSWX_WARP_MAX_SHIFT: a mesh node every 1 << shift destination pixels */
+    int32_t  has_nodata;               /* 0: every finite value is valid */
+    uint32_t nodata;                   /* float32: the bits of the value; int16: the value as int32 */
+    uint32_t outside;                  /* its low bytes are the element of an OUTSIDE pixel */
+    int32_t  reserved;                 /* must be 0 */
+    int32_t  reserved2;                /* must be 0 (padding in front of the 64-bit strides) */
+    int64_t  src_tile_stride;          /* elements between the tiles of the plane; 0 = height * width */
+    int64_t  mesh_tile_stride_nodes;   /* nodes between the meshes of consecutive tiles; 0 = one mesh for all tiles */
+} dswx_resample_spec_t;                /* 48 bytes */
+typedef struct dswx_resample_out {
+    void*     dst;                     /* [n_tiles][dst_h * dst_w] float32 or int16; NULL = not wanted */
+    uint8_t*  how;                     /* [n_tiles][dst_h * dst_w]; NULL = not wanted */
+    uint64_t* head;                    /* [n_tiles][8]; NULL = not wanted */
+} dswx_resample_out_t;
+/* One plane in DEVICE memory, resampled through mesh_device (DEVICE memory) -> the wanted outputs of *out_device (device
+ * memory).  Asynchronous on `stream` (NULL = the context's stream): one hipMemsetAsync of `head` (only if wanted) and ONE
+ * kernel launch, whatever the tile count (past the 65535 tiles of grid.y the workgroups walk the tiles); no synchronisation,
+ * no scratch of the context, no allocation, nothing the caller has to zero in front: a second call on the same outputs gives
+ * the same bytes, and no workgroup ever waits for another.  The refusals are those of dswx_warp_device with `kind` (not
+ * DSWX_RESAMPLE_F32 / _I16) and `method` (not _BILINEAR / _CUBIC) in the place of elem_bytes and `how` in the place of
+ * src_index: DSWX_ERR_ARG; mesh off 4 bytes, head off 8, plane or dst off the element size: DSWX_ERR_ALIGN.  The arguments
+ * are checked before the context is, and a refused call writes nothing.  Overlap of the outputs with the plane, the mesh or
+ * each other is NOT CHECKED. */
+int dswx_resample_device(dswx_ctx_t* ctx, const void* plane, const dswx_resample_spec_t* spec, int64_t n_tiles, int64_t height,
+                         int64_t width, const int32_t* mesh_device, int64_t dst_h, int64_t dst_w,
+                         const dswx_resample_out_t* out_device, void* stream);
+/* The same definition on HOST buffers in plain scalar C++, with a HOST mesh: needs no device and no context.  The other half of
+ * a comparison, not a fallback.  The refusals of dswx_resample_device, except that every buffer may sit at any address. */
+int dswx_resample_host(const void* plane, const dswx_resample_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                       const int32_t* mesh_host, int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out_host);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1440,7 +1526,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* / dswx_*warp* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* / dswx_*warp* / dswx_*resample* call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -50,7 +50,8 @@ EXPORTED_SYMBOLS = (
     'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host',
     'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host',
     'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host',
-    'dswx_warp_device', 'dswx_batch_warp', 'dswx_warp_host')
+    'dswx_warp_device', 'dswx_batch_warp', 'dswx_warp_host',
+    'dswx_resample_device', 'dswx_resample_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -91,6 +92,11 @@ WARP_HEAD_WORDS, WARP_MAX_SHIFT, WARP_OUTSIDE, WARP_MAX_PIXELS = 8, 8, 0xFFFFFFF
 # csrc/dswx_warp.hip: the rows and the columns of the destination rectangle of one workgroup, the pixels of a thread, and the
 # shift below which a thread's pixels cross mesh cells (tests build shapes around the seams)
 WARP_RECT_H, WARP_RECT_W, WARP_UNIT, WARP_FINE_BELOW = 4, 1024, 16, 4
+HAS_RESAMPLE = 1                  # DSWX_HAS_RESAMPLE: additive to ABI v7
+RESAMPLE_HEAD_WORDS, RESAMPLE_F32, RESAMPLE_I16, RESAMPLE_BILINEAR, RESAMPLE_CUBIC = 8, 0, 1, 1, 2
+# csrc/dswx_resample_rule.h: the rows and the columns of the destination rectangle of one workgroup and the elements of the
+# source window that it stages in LDS (a larger source box gathers from global memory; tests build shapes around the seams)
+RESAMPLE_RECT_H, RESAMPLE_RECT_W, RESAMPLE_LDS_ELEMS = 8, 32, 4096
 
 
 class DswxError(RuntimeError):
@@ -239,6 +245,28 @@ class WarpOut(ctypes.Structure):
     @classmethod
     def of(cls, dst=None, src_index=None, head=None):
         return cls(dst or None, src_index or None, head or None)
+
+
+class ResampleSpec(ctypes.Structure):
+    """dswx_resample_spec_t; proteus_amd.resample.Spec is the Python form."""
+    _fields_ = [('kind', ctypes.c_int32), ('method', ctypes.c_int32), ('shift', ctypes.c_int32), ('has_nodata', ctypes.c_int32),
+                ('nodata', ctypes.c_uint32), ('outside', ctypes.c_uint32), ('reserved', ctypes.c_int32), ('reserved2', ctypes.c_int32),
+                ('src_tile_stride', ctypes.c_int64), ('mesh_tile_stride_nodes', ctypes.c_int64)]
+
+    @classmethod
+    def of(cls, spec):
+        return cls(int(spec.kind), int(spec.method), int(spec.shift), int(spec.has_nodata), int(spec.nodata_word) & 0xFFFFFFFF,
+                   int(spec.outside) & 0xFFFFFFFF, int(getattr(spec, 'reserved', 0)), 0, int(spec.src_tile_stride),
+                   int(spec.mesh_tile_stride_nodes))
+
+
+class ResampleOut(ctypes.Structure):
+    """dswx_resample_out_t: addresses, 0 / None = not wanted."""
+    _fields_ = [('dst', ctypes.c_void_p), ('how', ctypes.c_void_p), ('head', ctypes.c_void_p)]
+
+    @classmethod
+    def of(cls, dst=None, how=None, head=None):
+        return cls(dst or None, how or None, head or None)
 
 
 class GridSpec(ctypes.Structure):
@@ -551,6 +579,8 @@ def load_library(path=None):
         'dswx_warp_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp]),
         'dswx_batch_warp': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, i64, i64, vp, vp]),
         'dswx_warp_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
+        'dswx_resample_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp]),
+        'dswx_resample_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
         'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
@@ -1211,6 +1241,15 @@ class Context:
                                          int(height), int(width), ctypes.c_void_p(mesh_ptr), int(dst_h), int(dst_w),
                                          ctypes.byref(out), _stream_arg(stream)))
 
+    def resample_device(self, plane_ptr, spec, n_tiles, height, width, mesh_ptr, dst_h, dst_w, out, stream=None):
+        """dswx_resample_device: one device plane float32 or int16 [n_tiles][spec.src_tile_stride], every tile a height x width
+        raster, interpolated (bilinear or cubic) onto dst_h x dst_w through the device mesh int32 [mesh_h][mesh_w][2] at mesh_ptr
+        (a resample.Spec; include/dswx_hip.h "resample", proteus_amd/resample.py states the definition in numpy) -> the outputs
+        `out` names (a ResampleOut of device addresses); one memset of the head and one launch, asynchronous."""
+        _check(self.lib.dswx_resample_device(self.handle, ctypes.c_void_p(plane_ptr), ctypes.byref(ResampleSpec.of(spec)), int(n_tiles),
+                                             int(height), int(width), ctypes.c_void_p(mesh_ptr), int(dst_h), int(dst_w),
+                                             ctypes.byref(out), _stream_arg(stream)))
+
     def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
         onto cells by `spec` (a grid.Spec; include/dswx_hip.h "grid", proteus_amd/grid.py states the definition in numpy) ->
@@ -1462,6 +1501,39 @@ def warp_host(tiles, mesh, spec, dst_shape, want=('dst', 'src_index', 'head'), r
     out = WarpOut.of(**{k: a.ctypes.data for k, a in res.items()})
     _check(load_library().dswx_warp_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(WarpSpec.of(spec)), n, int(H), int(W),
                                          _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
+    return res
+
+
+def _resample_planes(want, elem_dtype, n, dst_shape, make):
+    """{name: plane} for the outputs of a resample named in `want`, each made by make(shape, dtype)."""
+    dh, dw = (max(int(v), 0) for v in dst_shape)
+    shapes = {'dst': ((n, dh, dw), elem_dtype), 'how': ((n, dh, dw), np.uint8), 'head': ((n, RESAMPLE_HEAD_WORDS), np.uint64)}
+    want = _wanted(want, shapes)
+    return {k: make(*shapes[k]) for k in shapes if k in want}
+
+
+def resample_host(tiles, mesh, spec, dst_shape, want=('dst', 'how', 'head'), raster=None):
+    """dswx_resample_host (no device needed): the outputs of proteus_amd.resample.resample_tiles named in `want` -- 'dst'
+    [n, dst_h, dst_w] of the plane's dtype, 'how' uint8 [n, dst_h, dst_w], 'head' uint64 [n, 8] -- of a host plane float32 or
+    int16 [n_tiles, H, W] interpolated through the int32 mesh `mesh` ([mesh_h, mesh_w, 2], or per tile at
+    spec.mesh_tile_stride_nodes) by `spec` (a resample.Spec), by the library's scalar statement of the definition.  With
+    raster=(H, W), `tiles` is a padded plane [n_tiles, spec.src_tile_stride] whose padding is not read."""
+    tiles = np.ascontiguousarray(tiles)
+    if tiles.dtype != spec.dtype or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride] of {spec.dtype}, not {tiles.dtype} {tiles.shape}')
+    n = tiles.shape[0]
+    H, W = tiles.shape[1:] if raster is None else raster
+    mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+    dh, dw = (int(v) for v in dst_shape)
+    if dh > 0 and dw > 0 and 0 <= spec.shift <= WARP_MAX_SHIFT:
+        step = 1 << spec.shift
+        nodes = (((dh + step - 1) >> spec.shift) + 1) * (((dw + step - 1) >> spec.shift) + 1)
+        if mesh.size < 2 * (max(n - 1, 0) * spec.mesh_tile_stride_nodes + nodes):
+            raise ValueError(f'a mesh for {dh} x {dw} at shift {spec.shift} has {nodes} nodes per tile, {mesh.shape} is too small')
+    res = _resample_planes(want, tiles.dtype, n, (dh, dw), lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = ResampleOut.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(load_library().dswx_resample_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(ResampleSpec.of(spec)), n, int(H), int(W),
+                                             _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
     return res
 
 

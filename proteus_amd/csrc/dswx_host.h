@@ -321,6 +321,9 @@ int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_t
                     const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, int64_t* src_stride, bool align);
 int dswx_warp_launch(dswx_ctx* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                      int64_t src_stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, hipStream_t s);
+// the geometry half of dswx_warp_check, which the resample entries (dswx_resample.hip) share: shift, reserved, sizes, strides
+int dswx_mesh_geometry_check(int shift, int reserved, int64_t src_tile_stride, int64_t mesh_tile_stride_nodes, int64_t n_tiles,
+                             int64_t height, int64_t width, int64_t dst_h, int64_t dst_w, int64_t* src_stride);
 
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,

@@ -338,6 +338,35 @@ template <typename T> inline void put_at(void* base, int64_t i, T v) {
 
 }  // namespace
 
+// What every entry that reads a plane through a mesh checks of its geometry (the warp and the resample entries), with the
+// texts of the warp entries: shift, reserved, sizes, strides.  Resolves the stride of the plane (0 = height * width).
+int dswx_mesh_geometry_check(int shift, int reserved, int64_t src_tile_stride, int64_t mesh_tile_stride_nodes, int64_t n_tiles,
+                             int64_t height, int64_t width, int64_t dst_h, int64_t dst_w, int64_t* src_stride) {
+    if (shift < 0 || shift > DSWX_WARP_MAX_SHIFT)
+        return dswx_fail(DSWX_ERR_ARG, "shift %d outside 0 .. %d", shift, DSWX_WARP_MAX_SHIFT);
+    if (reserved != 0) return dswx_fail(DSWX_ERR_ARG, "reserved is %d, not 0", reserved);
+    if (n_tiles < 0 || height < 0 || width < 0 || dst_h < 0 || dst_w < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
+    if (src_tile_stride < 0 || mesh_tile_stride_nodes < 0) return dswx_fail(DSWX_ERR_ARG, "negative stride");
+    if (height > WARP_MAX_PIXELS || width > WARP_MAX_PIXELS || (width && height > WARP_MAX_PIXELS / width))
+        return dswx_fail(DSWX_ERR_ARG, "raster %lld x %lld above 2^30 pixels", (long long)height, (long long)width);
+    if (dst_h > WARP_MAX_PIXELS || dst_w > WARP_MAX_PIXELS || (dst_w && dst_h > WARP_MAX_PIXELS / dst_w))
+        return dswx_fail(DSWX_ERR_ARG, "destination %lld x %lld above 2^30 pixels", (long long)dst_h, (long long)dst_w);
+    const int64_t n_elems = height * width;
+    *src_stride = src_tile_stride ? src_tile_stride : n_elems;
+    if (*src_stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "src_tile_stride smaller than the tile");
+    const int64_t step = 1LL << shift;
+    const int64_t mesh_h = ((dst_h + step - 1) >> shift) + 1, mesh_w = ((dst_w + step - 1) >> shift) + 1;
+    if (mesh_tile_stride_nodes && mesh_tile_stride_nodes < mesh_h * mesh_w)
+        return dswx_fail(DSWX_ERR_ARG, "mesh_tile_stride_nodes %lld smaller than the mesh (%lld x %lld nodes)",
+                         (long long)mesh_tile_stride_nodes, (long long)mesh_h, (long long)mesh_w);
+    if (n_tiles > (1LL << 32)) return dswx_fail(DSWX_ERR_ARG, "more than 2^32 tiles");
+    if (*src_stride > (1LL << 46) || (n_tiles && (uint64_t)*src_stride > (1ull << 46) / (uint64_t)n_tiles))
+        return dswx_fail(DSWX_ERR_ARG, "plane too large");
+    if (mesh_tile_stride_nodes > (1LL << 46) || (n_tiles && (uint64_t)mesh_tile_stride_nodes > (1ull << 46) / (uint64_t)n_tiles))
+        return dswx_fail(DSWX_ERR_ARG, "mesh too large");
+    return DSWX_OK;
+}
+
 // The checks that the device and the host entry share, in the house order: the arguments before any context, nothing written by
 // a refused call.  Resolves the two strides of the spec (0 = height * width; 0 = shared mesh stays 0).  `align`: the device entry.
 int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
@@ -346,28 +375,10 @@ int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_t
     if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
     if (spec->elem_bytes != 1 && spec->elem_bytes != 2 && spec->elem_bytes != 4)
         return dswx_fail(DSWX_ERR_ARG, "elem_bytes %d: not 1, 2 or 4", spec->elem_bytes);
-    if (spec->shift < 0 || spec->shift > DSWX_WARP_MAX_SHIFT)
-        return dswx_fail(DSWX_ERR_ARG, "shift %d outside 0 .. %d", spec->shift, DSWX_WARP_MAX_SHIFT);
-    if (spec->reserved != 0) return dswx_fail(DSWX_ERR_ARG, "reserved is %d, not 0", spec->reserved);
-    if (n_tiles < 0 || height < 0 || width < 0 || dst_h < 0 || dst_w < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
-    if (spec->src_tile_stride < 0 || spec->mesh_tile_stride_nodes < 0) return dswx_fail(DSWX_ERR_ARG, "negative stride");
-    if (height > WARP_MAX_PIXELS || width > WARP_MAX_PIXELS || (width && height > WARP_MAX_PIXELS / width))
-        return dswx_fail(DSWX_ERR_ARG, "raster %lld x %lld above 2^30 pixels", (long long)height, (long long)width);
-    if (dst_h > WARP_MAX_PIXELS || dst_w > WARP_MAX_PIXELS || (dst_w && dst_h > WARP_MAX_PIXELS / dst_w))
-        return dswx_fail(DSWX_ERR_ARG, "destination %lld x %lld above 2^30 pixels", (long long)dst_h, (long long)dst_w);
+    if (int rc = dswx_mesh_geometry_check(spec->shift, spec->reserved, spec->src_tile_stride, spec->mesh_tile_stride_nodes, n_tiles, height,
+                                          width, dst_h, dst_w, src_stride))
+        return rc;
     const int64_t n_elems = height * width;
-    *src_stride = spec->src_tile_stride ? spec->src_tile_stride : n_elems;
-    if (*src_stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "src_tile_stride smaller than the tile");
-    const int64_t step = 1LL << spec->shift;
-    const int64_t mesh_h = ((dst_h + step - 1) >> spec->shift) + 1, mesh_w = ((dst_w + step - 1) >> spec->shift) + 1;
-    if (spec->mesh_tile_stride_nodes && spec->mesh_tile_stride_nodes < mesh_h * mesh_w)
-        return dswx_fail(DSWX_ERR_ARG, "mesh_tile_stride_nodes %lld smaller than the mesh (%lld x %lld nodes)",
-                         (long long)spec->mesh_tile_stride_nodes, (long long)mesh_h, (long long)mesh_w);
-    if (n_tiles > (1LL << 32)) return dswx_fail(DSWX_ERR_ARG, "more than 2^32 tiles");
-    if (*src_stride > (1LL << 46) || (n_tiles && (uint64_t)*src_stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
-    if (spec->mesh_tile_stride_nodes > (1LL << 46) || (n_tiles && (uint64_t)spec->mesh_tile_stride_nodes > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "mesh too large");
     const bool work = n_tiles > 0 && dst_h > 0 && dst_w > 0 && (out->dst || out->src_index || out->head);
     if (work && !mesh) return dswx_fail(DSWX_ERR_ARG, "mesh is NULL");
     if (work && !plane && n_elems > 0 && out->dst) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");

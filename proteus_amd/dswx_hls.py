@@ -15,13 +15,20 @@ numpy implementation of that chain in this package: without the built library or
 without a GPU, generate_dswx_layers raises.
 
 What stays on the host and is NOT re-implemented here (out of scope):
-GDAL reprojection of DEM / land cover / shoreline, hillshade ('otsu' shadow masking) and HDF4
+GDAL reprojection of land cover / shoreline, hillshade ('otsu' shadow masking) and HDF4
 input.  GDAL is not installed in this image, so raster I/O goes through proteus_amd.geotiff.
-Ancillary FILES are accepted when they are already on the product grid -- `dem_file` on the HLS
-grid with a margin (-> GPU terrain-shadow kernel, SHAD and DEM layers), `landcover_file` on the
-HLS grid and `worldcover_file` on the grid three times finer (-> GPU LAND aggregation) -- i.e.
-what the reference's own `_warp` calls would hand to its per-pixel code; anything that still
-needs warping, and `shoreline_shapefile`, raises NotImplementedError.  Pre-gridded planes can
+`dem_file` is accepted on the HLS grid with a margin, or as a north-up raster in EPSG:4326 (a
+Copernicus DEM as it ships): then it is laid onto the
+HLS grid grown by DEM_MARGIN_IN_PIXELS through a coordinate mesh computed on the host
+(proteus_amd.warp) and interpolated on the device (cubic, include/dswx_hip.h "resample": this
+project's own definition, gdal.Warp's is not pinned) -> GPU terrain-shadow kernel, SHAD and DEM
+layers.  `landcover_file` must be on the HLS grid and `worldcover_file` on the grid three times
+finer (-> GPU LAND aggregation), i.e. what the reference's own `_warp` calls would hand to its
+per-pixel code.  A DEM off the grid in a WGS 84 / UTM zone or in the product's own SRS is
+resampled the same way only with the keyword extension `resample_projected_dem=True`: without
+it such a file is refused as it always was (a DEM a few metres off the grid is more often a
+mistake than an intention).  Land cover that still needs warping, a DEM in any other SRS and
+`shoreline_shapefile` raise NotImplementedError.  Pre-gridded planes can
 also be handed over directly with the `landcover_mask=`, `shadow_layer=` and `ocean_mask=`
 keyword extensions (arrays or GeoTIFF paths).
 """
@@ -1014,6 +1021,69 @@ def _get_landcover_mask_ctable():
     return ct
 
 
+DEM_MESH_SHIFTS = (6, 5, 4)                # tried in this order until the mesh deviates by at most 1/256 source pixel
+
+
+def dem_resample_plan(dem_info, geotransform, geo_tags, length, width, projected=False):
+    """What lays a DEM that is NOT on the HLS grid onto the HLS grid grown by DEM_MARGIN_IN_PIXELS on every side:
+    (window (xoff, yoff, xsize, ysize) of the DEM file to read, mesh int32 relative to that window, shift, deviation in 1/256
+    source pixel, destination shape).  The DEM must be a north-up raster in EPSG:4326 under a product in a WGS 84 / UTM zone;
+    with `projected`, also one in a WGS 84 / UTM zone or in the product's own SRS (warp.mesh_between decides)."""
+    from . import warp
+    src_gt = dem_info.geotransform
+    src_epsg, dst_epsg = warp.epsg_of(dem_info.geo_tags), warp.epsg_of(geo_tags)
+    m = DEM_MARGIN_IN_PIXELS
+    dst_gt = (geotransform[0] - m * geotransform[1], geotransform[1], 0.0, geotransform[3] - m * geotransform[5], 0.0, geotransform[5])
+    dst_shape = (length + 2 * m, width + 2 * m)
+    refusal = ('dem_file is not on the HLS grid (same pixel size, same margin on all sides) and not a north-up raster in EPSG:4326 '
+               'under a product in a WGS 84 / UTM zone, which is resampled on the device (so is, with resample_projected_dem=True, '
+               'one in a WGS 84 / UTM zone or in the SRS of the product): reprojecting it needs GDAL, which '
+               'stays on the host and is outside this drop-in (SURVEY.md section 2); warp it first or pass shadow_layer=')
+    geographic = src_gt is not None and src_epsg == warp.GEOGRAPHIC_EPSG and warp.in_degrees(src_gt)
+    if src_gt is None or dst_epsg is None or not (geographic or (projected and src_epsg is not None)):
+        raise NotImplementedError(refusal)
+    mesh = None
+    for shift in DEM_MESH_SHIFTS:
+        try:
+            mesh, deviation = warp.mesh_between(src_gt, src_epsg, dst_gt, dst_epsg, dst_shape, shift)
+        except ValueError as e:
+            raise NotImplementedError(f'{refusal} ({e})')
+        if deviation <= 1.0:
+            break
+    # the source window: the extent of the nodes, widened by the cubic halo and the deviation, clipped to the file
+    pad = 3 + int(np.ceil(deviation / 256.0))
+    x, y = mesh[..., 0].astype(np.int64), mesh[..., 1].astype(np.int64)
+    x0, x1 = max(int(x.min() >> 8) - pad, 0), min(int(x.max() >> 8) + pad + 1, dem_info.width)
+    y0, y1 = max(int(y.min() >> 8) - pad, 0), min(int(y.max() >> 8) + pad + 1, dem_info.height)
+    window = (x0, y0, max(x1 - x0, 0), max(y1 - y0, 0)) if x1 > x0 and y1 > y0 else (0, 0, 0, 0)
+    moved = np.clip(np.stack([x - 256 * window[0], y - 256 * window[1]], axis=-1), -(1 << 31), (1 << 31) - 1).astype(np.int32)
+    return window, moved, shift, deviation, dst_shape
+
+
+def _resample_dem(engine, dem_file, dem_dir, geotransform, geo_tags, length, width, projected=False):
+    """The DEM of `dem_file` (not on the HLS grid) -> DevicePlane float32 on the HLS grid with DEM_MARGIN_IN_PIXELS: the window
+    the mesh needs is read on the host, the cubic interpolation runs on the device (dswx_resample_device)."""
+    from . import resample
+    if dem_dir.spp != 1:
+        raise NotImplementedError(f'dem_file has {dem_dir.spp} bands: a DEM is one band')
+    info = dem_dir.info
+    window, mesh, shift, deviation, dst_shape = dem_resample_plan(info, geotransform, geo_tags, length, width, projected)
+    logger.info(f'    DEM is not on the HLS grid: cubic resampling on the device, mesh shift {shift}, '
+                f'deviation {deviation:.2f}/256 source pixel, source window {window}')
+    if window[2] == 0:
+        logger.warning('WARNING the DEM does not cover the HLS tile')
+        window = (0, 0, min(1, info.width), min(1, info.height))
+    src, _ = geotiff.read_geotiff(dem_file, window=window)
+    src = np.ascontiguousarray(src, dtype=np.float32)               # (the reference: np.asarray(..., dtype=np.float32))
+    nodata = info.nodata if info.nodata is not None and not np.isnan(info.nodata) else None
+    outside = resample.outside_word(info.nodata if info.nodata is not None else 0.0, np.float32)
+    plane = engine.upload(src)
+    try:
+        return plane.resample(mesh, dst_shape, shift, 'cubic', nodata=nodata, outside=outside)['dst']
+    finally:
+        plane.release()
+
+
 def _grid_margin(info, geotransform, length, width, scale=1):
     """If the raster described by `info` is on the HLS grid refined `scale` times and covers it
     with the same margin on all four sides, returns that margin in (refined) pixels; else None.
@@ -1159,10 +1229,12 @@ def generate_dswx_layers(input_list,
                          landcover_mask=None,
                          shadow_layer=None,
                          ocean_mask=None,
-                         device=None):
+                         device=None,
+                         resample_projected_dem=False):
     """Compute the DSWx-HLS layers of one HLS tile; same signature and return value as the
-    reference (:4610-4657) plus four keyword-only extensions (pre-gridded LAND / SHAD /
-    ocean planes, and the GPU to use).  Returns True, or False after logging 'ERROR ...'
+    reference (:4610-4657) plus five keyword-only extensions (pre-gridded LAND / SHAD /
+    ocean planes, the GPU to use, and whether a `dem_file` off the HLS grid in a WGS 84 / UTM
+    zone or in the product's own SRS is resampled like one in EPSG:4326 instead of refused).  Returns True, or False after logging 'ERROR ...'
     when the input cannot be read (:4988-4990)."""
     _DeferredWrites.reset()                # a previous run that raised must not leave writes deferred
     local = locals()
@@ -1303,13 +1375,14 @@ def generate_dswx_layers(input_list,
             dem_info = dem_dir.info
             margin = _grid_margin(dem_info, image['geotransform'], length, width) if dem_dir.spp == 1 else None
             if margin is None:
-                raise NotImplementedError(
-                    'dem_file is not on the HLS grid (same pixel size, same margin on all sides): '
-                    'reprojecting it needs GDAL, which stays on the host and is outside this drop-in '
-                    '(SURVEY.md section 2); warp it first or pass shadow_layer=')
-            dem_with_margin, _ = engine.read_directory(dem_dir)
-            if dem_with_margin.dtype != np.float32:                 # (the reference: np.asarray(..., dtype=np.float32))
-                dem_with_margin = engine.upload(np.ascontiguousarray(dem_with_margin.numpy(), dtype=np.float32))
+                # :5145-5150, `_warp(dem_file, ..., resample_algorithm='cubic', margin_in_pixels=50)`: on the device
+                dem_with_margin = _resample_dem(engine, dem_file, dem_dir, image['geotransform'], geo_tags, length, width,
+                                                resample_projected_dem)
+                margin = DEM_MARGIN_IN_PIXELS
+            else:
+                dem_with_margin, _ = engine.read_directory(dem_dir)
+                if dem_with_margin.dtype != np.float32:             # (the reference: np.asarray(..., dtype=np.float32))
+                    dem_with_margin = engine.upload(np.ascontiguousarray(dem_with_margin.numpy(), dtype=np.float32))
         if margin > DEM_MARGIN_IN_PIXELS:
             dem_with_margin = engine.crop(dem_with_margin, margin - DEM_MARGIN_IN_PIXELS)
             margin = DEM_MARGIN_IN_PIXELS

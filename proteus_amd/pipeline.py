@@ -187,6 +187,40 @@ class DevicePlane:
             table.release()
         return made
 
+    def resample(self, mesh, dst_shape, shift, method='cubic', nodata=None, outside=0, want=('dst',)):
+        """The rasters of a float32 or int16 [n, H, W] (or one [H, W]) plane INTERPOLATED -- 'bilinear' or 'cubic' -- onto
+        dst_shape = (dst_h, dst_w) through `mesh` (as for `warp`) as they lie in HBM (dswx_resample_device;
+        proteus_amd.resample.resample_tiles of the same arrays gives the same arrays).  `nodata`: the value of a tap that is
+        not valid (None: every finite value is); `outside`: a uint32 whose low bytes are the element of a pixel without a valid
+        tap (resample.outside_word).  A dict of DevicePlanes for the outputs named in `want` -- 'dst' [n, dst_h, dst_w] of this
+        plane's dtype ([dst_h, dst_w] for one raster), 'how' uint8 of the same shape, 'head' uint64 [n, 8] -- which stay on the
+        device: the DEM of a product run goes on to the shadow kernel."""
+        from . import resample as _resample, warp as _warp
+        if len(self.shape) not in (2, 3):
+            raise ValueError(f'a resample is made of a [n, H, W] or [H, W] plane, not {self.shape}')
+        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
+        height, width = self.shape[-2:]
+        shape = tuple(int(v) for v in dst_shape)
+        if len(shape) != 2 or min(shape) < 0 or shape[0] * shape[1] > _capi.WARP_MAX_PIXELS:
+            raise ValueError(f'a destination is (dst_h, dst_w) of at most {_capi.WARP_MAX_PIXELS} pixels, not {dst_shape}')
+        mh, mw = _warp.mesh_shape(shape, shift)
+        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+        if mesh.shape not in ((mh, mw, 2), (n_tiles, mh, mw, 2)):
+            raise ValueError(f'a mesh for {shape} at shift {shift} is [{mh}, {mw}, 2] or [{n_tiles}, {mh}, {mw}, 2], not {mesh.shape}')
+        spec = _resample.Spec(self.dtype, method, shift, nodata, outside, mesh_tile_stride_nodes=mh * mw if mesh.ndim == 4 else 0)
+        lead = (n_tiles,) if len(self.shape) == 3 else ()
+        made = _capi._resample_planes(want, self.dtype, n_tiles, shape,
+                                      lambda shp, dt: self.engine.plane(shp if len(shp) == 2 else lead + tuple(shp[1:]), dt))
+        out = _capi.ResampleOut.of(**{k: p.ptr for k, p in made.items()})
+        table = self.engine.upload(mesh)
+        try:
+            with self.engine.lock, stages.span('gpu: resample'):
+                self.engine.ctx.resample_device(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
+                self.engine.ctx.synchronize()
+        finally:
+            table.release()
+        return made
+
     def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
         """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;
         proteus_amd.grid.grid_tiles of the same array gives the same planes): a dict of [n, GH, GW] DevicePlanes for the

@@ -244,21 +244,59 @@ def _utm_exact(src_gt, src_epsg, dst_gt, dst_epsg, Y, X):
     return (x - src_gt[0]) / src_gt[1], (y - src_gt[3]) / src_gt[5]
 
 
+def _mesh_and_deviation(exact, dst_shape, shift):
+    """(mesh, deviation) of exact(Y, X) -> continuous source pixel coordinates (col, row): the nodes quantised, and the largest
+    deviation of the interpolated mesh from the exact mapping at the CENTRES of the mesh cells, in 1/256 source pixel."""
+    Y, X = _node_pixels(dst_shape, shift)
+    col, row = exact(Y, X)
+    mesh = _quantise(col, row)
+    half = (1 << shift) / 2.0
+    ccol, crow = exact(Y[:-1] + half, X[:, :-1] + half)
+    m = mesh.astype(np.float64)
+    mid = (m[:-1, :-1] + m[:-1, 1:] + m[1:, :-1] + m[1:, 1:]) / 4.0
+    dev = np.maximum(np.abs(mid[..., 0] - 256.0 * ccol), np.abs(mid[..., 1] - 256.0 * crow))
+    return mesh, float(dev.max()) if dev.size else 0.0
+
+
 def utm_mesh(src_gt, src_epsg, dst_gt, dst_epsg, dst_shape, shift):
     """(mesh int32 [mesh_h, mesh_w, 2], deviation): the mesh that lays a source raster (north-up geotransform src_gt, EPSG
     326zz / 327zz) onto a destination of dst_shape with dst_gt in another -- or the same -- WGS 84 / UTM zone, and the largest
     deviation of the interpolated mesh from the exact mapping at the CENTRES of the mesh cells, in 1/256 source pixel, so that a
     caller can choose `shift`.  Positions beyond int32 are clamped to INT32_MIN / INT32_MAX."""
     s, d = _north_up(src_gt, 'the source'), _north_up(dst_gt, 'the destination')
+    return _mesh_and_deviation(lambda Y, X: _utm_exact(s, src_epsg, d, dst_epsg, Y, X), dst_shape, shift)
+
+
+GEOGRAPHIC_EPSG = 4326
+
+
+def _geographic_exact(src_gt, dst_gt, dst_epsg, Y, X):
+    """Continuous source pixel coordinates (col, row) in a north-up raster in degrees (EPSG:4326) of the centres of destination
+    pixels (X, Y) of a WGS 84 / UTM grid (floats allowed), and the longitudes: destination pixel centre -> tm_inverse -> pixel."""
+    lon0, fn = utm_zone(dst_epsg)
+    lon, lat = tm_inverse(dst_gt[0] + (X + 0.5) * dst_gt[1] + 0.0 * Y - UTM_FALSE_EASTING, dst_gt[3] + (Y + 0.5) * dst_gt[5] + 0.0 * X - fn, lon0)
+    return (lon - src_gt[0]) / src_gt[1], (lat - src_gt[3]) / src_gt[5], lon
+
+
+def geographic_mesh(src_gt, dst_gt, dst_epsg, dst_shape, shift):
+    """(mesh int32 [mesh_h, mesh_w, 2], deviation) as utm_mesh reports them, for a source raster in EPSG:4326 (north-up
+    geotransform src_gt in degrees: a DEM) laid onto a destination of dst_shape with dst_gt in a WGS 84 / UTM zone (dst_epsg
+    326zz / 327zz).  A destination whose nodes leave -180 .. 180 degrees of longitude is refused: the antimeridian is out of
+    scope."""
+    s, d = _north_up(src_gt, 'the source'), _north_up(dst_gt, 'the destination')
     Y, X = _node_pixels(dst_shape, shift)
-    col, row = _utm_exact(s, src_epsg, d, dst_epsg, Y, X)
-    mesh = _quantise(col, row)
-    half = (1 << shift) / 2.0
-    ccol, crow = _utm_exact(s, src_epsg, d, dst_epsg, Y[:-1] + half, X[:, :-1] + half)
-    m = mesh.astype(np.float64)
-    mid = (m[:-1, :-1] + m[:-1, 1:] + m[1:, :-1] + m[1:, 1:]) / 4.0
-    dev = np.maximum(np.abs(mid[..., 0] - 256.0 * ccol), np.abs(mid[..., 1] - 256.0 * crow))
-    return mesh, float(dev.max()) if dev.size else 0.0
+    lon = _geographic_exact(s, d, dst_epsg, Y, X)[2]
+    if lon.size and (float(lon.min()) < -180.0 or float(lon.max()) > 180.0):
+        raise ValueError(f'the destination reaches {float(lon.min()):.4f} .. {float(lon.max()):.4f} degrees of longitude: the source window '
+                         'would cross the antimeridian, which is not handled')
+    return _mesh_and_deviation(lambda Y, X: _geographic_exact(s, d, dst_epsg, Y, X)[:2], dst_shape, shift)
+
+
+def in_degrees(src_gt):
+    """Whether the origin of a north-up geotransform can be one in degrees: a longitude in -180 .. 180, a latitude in -90 ..
+    90, and a pixel smaller than a degree.  A geotransform in metres that merely carries the code 4326 is not."""
+    gt = tuple(float(v) for v in src_gt)
+    return len(gt) == 6 and -180.0 <= gt[0] <= 180.0 and -90.0 <= gt[3] <= 90.0 and 0.0 < abs(gt[1]) < 1.0 and 0.0 < abs(gt[5]) < 1.0
 
 
 def epsg_of(geo_tags):
@@ -273,7 +311,11 @@ def epsg_of(geo_tags):
 
 def mesh_between(src_gt, src_epsg, dst_gt, dst_epsg, dst_shape, shift):
     """(mesh, deviation) for two rasters by their geotransforms and EPSG codes: affine_mesh when the codes are equal (any SRS,
-    None included), utm_mesh for two WGS 84 / UTM zones; refused otherwise."""
+    None included), geographic_mesh for a source in EPSG:4326 whose geotransform is in degrees (in_degrees) under a WGS 84 / UTM
+    destination, utm_mesh for two WGS 84 / UTM zones; refused otherwise -- a source that carries the code 4326 over a
+    geotransform in metres included."""
     if src_epsg == dst_epsg:
         return affine_mesh(src_gt, dst_gt, dst_shape, shift), 0.0
+    if src_epsg == GEOGRAPHIC_EPSG and in_degrees(src_gt):
+        return geographic_mesh(src_gt, dst_gt, dst_epsg, dst_shape, shift)
     return utm_mesh(src_gt, src_epsg, dst_gt, dst_epsg, dst_shape, shift)
