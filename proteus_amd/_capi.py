@@ -1475,12 +1475,40 @@ def mosaic_host(tiles, place, canvas_shape, spec, want=('count', 'last', 'last_i
     return res
 
 
-def _warp_planes(want, elem_dtype, n, dst_shape, make):
-    """{name: plane} for the outputs of a warp named in `want`, each made by make(shape, dtype)."""
+def _mesh_planes(want, elem_dtype, n, dst_shape, make, second, head_words):
+    """{name: plane} for the outputs of a warp or a resample named in `want`, each made by make(shape, dtype): 'dst', the
+    per-pixel plane `second` = (name, dtype) and 'head'."""
     dh, dw = (max(int(v), 0) for v in dst_shape)
-    shapes = {'dst': ((n, dh, dw), elem_dtype), 'src_index': ((n, dh, dw), np.uint32), 'head': ((n, WARP_HEAD_WORDS), np.uint64)}
+    shapes = {'dst': ((n, dh, dw), elem_dtype), second[0]: ((n, dh, dw), second[1]), 'head': ((n, head_words), np.uint64)}
     want = _wanted(want, shapes)
     return {k: make(*shapes[k]) for k in shapes if k in want}
+
+
+def _mesh_host(entry, planes, spec_type, out_type, tiles, elem_ok, elems, mesh, spec, dst_shape, want, raster):
+    """The host entry `entry` of a warp or a resample on a host plane and a host mesh: the shape checks, the node count that
+    the entry itself cannot check (it has an address, not an array), the outputs and the call."""
+    tiles = np.ascontiguousarray(tiles)
+    if not elem_ok(tiles.dtype) or tiles.ndim != (3 if raster is None else 2):
+        raise ValueError(f'a plane is [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride] of {elems}, not {tiles.dtype} {tiles.shape}')
+    n = tiles.shape[0]
+    H, W = tiles.shape[1:] if raster is None else raster
+    mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+    dh, dw = (int(v) for v in dst_shape)
+    if n > 0 and dh > 0 and dw > 0 and 0 <= spec.shift <= WARP_MAX_SHIFT:            # (else the entry reads no node)
+        step = 1 << spec.shift
+        nodes = (((dh + step - 1) >> spec.shift) + 1) * (((dw + step - 1) >> spec.shift) + 1)
+        if mesh.size < 2 * ((n - 1) * spec.mesh_tile_stride_nodes + nodes):
+            raise ValueError(f'a mesh for {dh} x {dw} at shift {spec.shift} has {nodes} nodes per tile, {mesh.shape} is too small')
+    res = planes(want, tiles.dtype, n, (dh, dw), lambda shp, dt: np.zeros(shp, dtype=dt))
+    out = out_type.of(**{k: a.ctypes.data for k, a in res.items()})
+    _check(getattr(load_library(), entry)(_host_ptr(tiles) if tiles.size else None, ctypes.byref(spec_type.of(spec)), n, int(H), int(W),
+                                          _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
+    return res
+
+
+def _warp_planes(want, elem_dtype, n, dst_shape, make):
+    """{name: plane} for the outputs of a warp named in `want`, each made by make(shape, dtype)."""
+    return _mesh_planes(want, elem_dtype, n, dst_shape, make, ('src_index', np.uint32), WARP_HEAD_WORDS)
 
 
 def warp_host(tiles, mesh, spec, dst_shape, want=('dst', 'src_index', 'head'), raster=None):
@@ -1489,27 +1517,13 @@ def warp_host(tiles, mesh, spec, dst_shape, want=('dst', 'src_index', 'head'), r
     or 4 bytes per element warped through the int32 mesh `mesh` ([mesh_h, mesh_w, 2], or per tile at
     spec.mesh_tile_stride_nodes) by `spec` (a warp.Spec), by the library's scalar statement of the definition.  With
     raster=(H, W), `tiles` is a padded plane [n_tiles, spec.src_tile_stride] whose padding is not read."""
-    tiles = np.ascontiguousarray(tiles)
-    if tiles.dtype.itemsize != spec.elem_bytes or tiles.ndim != (3 if raster is None else 2):
-        raise ValueError(f'a plane is [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride] of {spec.elem_bytes}-byte elements, '
-                         f'not {tiles.dtype} {tiles.shape}')
-    n = tiles.shape[0]
-    H, W = tiles.shape[1:] if raster is None else raster
-    mesh = np.ascontiguousarray(mesh, dtype=np.int32)
-    dh, dw = (int(v) for v in dst_shape)
-    res = _warp_planes(want, tiles.dtype, n, (dh, dw), lambda shp, dt: np.zeros(shp, dtype=dt))
-    out = WarpOut.of(**{k: a.ctypes.data for k, a in res.items()})
-    _check(load_library().dswx_warp_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(WarpSpec.of(spec)), n, int(H), int(W),
-                                         _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
-    return res
+    return _mesh_host('dswx_warp_host', _warp_planes, WarpSpec, WarpOut, tiles, lambda dt: dt.itemsize == spec.elem_bytes,
+                      f'{spec.elem_bytes}-byte elements', mesh, spec, dst_shape, want, raster)
 
 
 def _resample_planes(want, elem_dtype, n, dst_shape, make):
     """{name: plane} for the outputs of a resample named in `want`, each made by make(shape, dtype)."""
-    dh, dw = (max(int(v), 0) for v in dst_shape)
-    shapes = {'dst': ((n, dh, dw), elem_dtype), 'how': ((n, dh, dw), np.uint8), 'head': ((n, RESAMPLE_HEAD_WORDS), np.uint64)}
-    want = _wanted(want, shapes)
-    return {k: make(*shapes[k]) for k in shapes if k in want}
+    return _mesh_planes(want, elem_dtype, n, dst_shape, make, ('how', np.uint8), RESAMPLE_HEAD_WORDS)
 
 
 def resample_host(tiles, mesh, spec, dst_shape, want=('dst', 'how', 'head'), raster=None):
@@ -1518,23 +1532,8 @@ def resample_host(tiles, mesh, spec, dst_shape, want=('dst', 'how', 'head'), ras
     int16 [n_tiles, H, W] interpolated through the int32 mesh `mesh` ([mesh_h, mesh_w, 2], or per tile at
     spec.mesh_tile_stride_nodes) by `spec` (a resample.Spec), by the library's scalar statement of the definition.  With
     raster=(H, W), `tiles` is a padded plane [n_tiles, spec.src_tile_stride] whose padding is not read."""
-    tiles = np.ascontiguousarray(tiles)
-    if tiles.dtype != spec.dtype or tiles.ndim != (3 if raster is None else 2):
-        raise ValueError(f'a plane is [n_tiles, H, W] or, with raster=, [n_tiles, tile_stride] of {spec.dtype}, not {tiles.dtype} {tiles.shape}')
-    n = tiles.shape[0]
-    H, W = tiles.shape[1:] if raster is None else raster
-    mesh = np.ascontiguousarray(mesh, dtype=np.int32)
-    dh, dw = (int(v) for v in dst_shape)
-    if dh > 0 and dw > 0 and 0 <= spec.shift <= WARP_MAX_SHIFT:
-        step = 1 << spec.shift
-        nodes = (((dh + step - 1) >> spec.shift) + 1) * (((dw + step - 1) >> spec.shift) + 1)
-        if mesh.size < 2 * (max(n - 1, 0) * spec.mesh_tile_stride_nodes + nodes):
-            raise ValueError(f'a mesh for {dh} x {dw} at shift {spec.shift} has {nodes} nodes per tile, {mesh.shape} is too small')
-    res = _resample_planes(want, tiles.dtype, n, (dh, dw), lambda shp, dt: np.zeros(shp, dtype=dt))
-    out = ResampleOut.of(**{k: a.ctypes.data for k, a in res.items()})
-    _check(load_library().dswx_resample_host(_host_ptr(tiles) if tiles.size else None, ctypes.byref(ResampleSpec.of(spec)), n, int(H), int(W),
-                                             _host_ptr(mesh) if mesh.size else None, dh, dw, ctypes.byref(out)))
-    return res
+    return _mesh_host('dswx_resample_host', _resample_planes, ResampleSpec, ResampleOut, tiles, lambda dt: dt == spec.dtype,
+                      spec.dtype, mesh, spec, dst_shape, want, raster)
 
 
 def _stack_planes(want, spec, shape, make):

@@ -33,7 +33,7 @@ HEADERS = [os.path.join(CSRC, n) for n in ('dswx_device.h', 'dswx_host.h', 'dswx
                                            'dswx_hist_bin.h', 'dswx_stack_rule.h', 'dswx_grid_rule.h',
                                            'dswx_label_rule.h', 'dswx_body_rule.h', 'dswx_distance_rule.h',
                                            'dswx_outline_rule.h', 'dswx_burn_rule.h', 'dswx_batch_select.h',
-                                           'dswx_resample_rule.h')]
+                                           'dswx_mesh_rule.h', 'dswx_resample_rule.h')]
 LAB_SOURCES = [os.path.join(LAB, n) for n in ('dswx_lab.hip', 'dswx_probes.hip')]
 LAB_HEADERS = [os.path.join(LAB, 'dswx_lab.h')]
 INCLUDE = os.path.join(ROOT, 'include')

@@ -9,6 +9,7 @@
 #include <string>
 
 #include "dswx_device.h"
+#include "dswx_mesh_rule.h"
 
 // A grow-only device allocation of a context.
 struct dswx_workspace {
@@ -321,9 +322,47 @@ int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_t
                     const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, int64_t* src_stride, bool align);
 int dswx_warp_launch(dswx_ctx* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                      int64_t src_stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, hipStream_t s);
-// the geometry half of dswx_warp_check, which the resample entries (dswx_resample.hip) share: shift, reserved, sizes, strides
+// ---- what the warp and the resample entries (dswx_resample.hip) share, defined in dswx_warp.hip.  The geometry half of their
+// checks: shift, reserved, sizes, strides
 int dswx_mesh_geometry_check(int shift, int reserved, int64_t src_tile_stride, int64_t mesh_tile_stride_nodes, int64_t n_tiles,
                              int64_t height, int64_t width, int64_t dst_h, int64_t dst_w, int64_t* src_stride);
+// is there anything to do: tiles, destination pixels and an output that is wanted
+static inline bool dswx_mesh_work(int64_t n_tiles, int64_t dst_h, int64_t dst_w, bool wanted) {
+    return n_tiles > 0 && dst_h > 0 && dst_w > 0 && wanted;
+}
+// the pointer half: a mesh and (if `plane_read`) a plane where there is work, then (`align`) mesh, src_index (NULL: none), head,
+// plane and dst
+int dswx_mesh_pointer_check(bool work, const void* plane, bool plane_read, int elem_bytes, const int32_t* mesh, const void* dst,
+                            const uint32_t* src_index, const uint64_t* head, bool align);
+// before the launch of either kernel: the fields that WarpArgs and ResArgs have in common, for rectangles of rect_h x rect_w
+// pixels; a wanted head (8 words per tile) set to 0xFF bytes; grid.y (past 65535 tiles the workgroups of a row walk the tiles)
+template <class Args>
+static inline int dswx_mesh_launch_prepare(Args& a, const void* plane, int64_t src_stride, int elem_bytes, const int32_t* mesh,
+                                           int64_t mesh_tile_stride_nodes, int shift, int64_t n_tiles, int64_t height, int64_t width,
+                                           int64_t dst_h, int64_t dst_w, int rect_h, int rect_w, void* dst, uint64_t* head, hipStream_t s,
+                                           unsigned* grid_y) {
+    static_assert(DSWX_WARP_HEAD_WORDS == 8 && DSWX_RESAMPLE_HEAD_WORDS == 8, "one head of 8 words per tile");
+    const unsigned long long nbx = ((unsigned long long)dst_w + rect_w - 1) / rect_w, nby = ((unsigned long long)dst_h + rect_h - 1) / rect_h;
+    a.plane = static_cast<const unsigned char*>(plane);
+    a.src_stride_bytes = (unsigned long long)src_stride * (unsigned)elem_bytes;
+    a.mesh = mesh;
+    a.mesh_stride_ints = 2ull * (unsigned long long)mesh_tile_stride_nodes;
+    a.n_tiles = (unsigned long long)n_tiles;
+    a.n_rects = nbx * nby;
+    a.dst_px = (unsigned long long)dst_h * (unsigned long long)dst_w;
+    a.height = (int)height;
+    a.width = (int)width;
+    a.dst_h = (int)dst_h;
+    a.dst_w = (int)dst_w;
+    a.shift = shift;
+    a.mesh_w = (int)mesh_dims(dst_w, shift);
+    a.nbx = (unsigned)nbx;
+    a.dst = static_cast<unsigned char*>(dst);
+    a.head = reinterpret_cast<unsigned long long*>(head);
+    if (head) HIP_TRY(hipMemsetAsync(head, 0xFF, (size_t)n_tiles * 8 * sizeof(uint64_t), s));
+    *grid_y = (unsigned)(n_tiles < 65535 ? n_tiles : 65535);
+    return DSWX_OK;
+}
 
 // ---- 'cover' mode stage 2 (dswx_cover.hip): appends its description to `info`
 int dswx_cover_stage2_launch(dswx_ctx* ctx, const KArgs& c2, long long n_tiles, hipStream_t stream, char* info,

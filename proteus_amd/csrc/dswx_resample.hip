@@ -15,10 +15,9 @@
 // kernel's 4 x 1024 strip: under a few degrees of rotation the source box of a strip is tall, that of a rectangle stays small.
 //
 // POSITIONS.  Every thread evaluates the definition's 64-bit form for its own pixel from the four nodes of its cell (eight
-// int32 loads that the threads of a rectangle share through the caches) through resample_position, which this kernel and
-// dswx_resample_host share.  It is a SECOND statement of the formula that dswx_warp.hip states for itself: the two are held
-// equal by the tests (tests/test_resample.py compares with the warp tests' loop_positions), not by shared code.  The warp
-// kernel's per-cell linear form was not used: a thread has one pixel, not sixteen.
+// int32 loads that the threads of a rectangle share through the caches) through mesh_position of dswx_mesh_rule.h, the one
+// statement of the formula, which this kernel, dswx_resample_host and dswx_warp_host execute.  The warp kernel's per-cell
+// linear form (mesh_cell_linear, in the same header) is not used: a thread has one pixel, not sixteen.
 //
 // TAPS.  The workgroup reduces the exact bounding box of the windows of its pixels (base pixel - 1 .. + 2 for cubic, 0 .. + 1
 // for bilinear), clipped to the raster; pixels whose whole window misses the raster do not count.  When the box has at most
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(RES_BLOCK) void dswx_resample_k(const ResArgs a) {
             int cl = INT_MAX, ch = -1, rl = INT_MAX, rh = -1;
             if (live) {
                 int64_t px, py;
-                resample_position([&](int64_t k) { return (int64_t)mesh[k]; }, a.shift, a.mesh_w, X, Y, &px, &py);
+                mesh_position([&](int64_t k) { return (int64_t)mesh[k]; }, a.shift, a.mesh_w, X, Y, &px, &py);
                 sx = px, sy = py;
                 const long long c0 = (sx - 128) >> 8, r0 = (sy - 128) >> 8;
                 // a window that meets the raster: its clipped sides are columns and rows of the raster, so they fit an int
@@ -221,13 +220,6 @@ __global__ __launch_bounds__(RES_BLOCK) void dswx_resample_k(const ResArgs a) {
     }
 }
 
-// unaligned host accesses (a host buffer may sit at any address)
-inline int64_t res_mesh_at(const int32_t* base, int64_t i) {
-    int32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
-}
-
 int resample_check(const void* plane, const dswx_resample_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width, const int32_t* mesh,
                    int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out, int64_t* src_stride, bool align) {
     if (!spec) return dswx_fail(DSWX_ERR_ARG, "spec is NULL");
@@ -240,17 +232,9 @@ int resample_check(const void* plane, const dswx_resample_spec_t* spec, int64_t 
     if (int rc = dswx_mesh_geometry_check(spec->shift, spec->reserved, spec->src_tile_stride,
                                           spec->mesh_tile_stride_nodes, n_tiles, height, width, dst_h, dst_w, src_stride))
         return rc;
-    const bool work = n_tiles > 0 && dst_h > 0 && dst_w > 0 && (out->dst || out->how || out->head);
-    if (work && !mesh) return dswx_fail(DSWX_ERR_ARG, "mesh is NULL");
-    if (work && !plane && height * width > 0) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");       // every output reads it
-    if (align) {
-        const size_t eb = spec->kind == DSWX_RESAMPLE_F32 ? 4 : 2;
-        if (!aligned_to(mesh, 4)) return dswx_fail(DSWX_ERR_ALIGN, "mesh not 4-byte aligned");
-        if (!aligned_to(out->head, 8)) return dswx_fail(DSWX_ERR_ALIGN, "head not 8-byte aligned");
-        if (!aligned_to(plane, eb)) return dswx_fail(DSWX_ERR_ALIGN, "plane not %d-byte aligned", (int)eb);
-        if (!aligned_to(out->dst, eb)) return dswx_fail(DSWX_ERR_ALIGN, "dst not %d-byte aligned", (int)eb);
-    }
-    return DSWX_OK;
+    const bool work = dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->how || out->head);
+    return dswx_mesh_pointer_check(work, plane, height * width > 0 /* every output reads it */, spec->kind == DSWX_RESAMPLE_F32 ? 4 : 2, mesh,
+                                   out->dst, nullptr, out->head, align);
 }
 
 template <bool F32>
@@ -258,7 +242,7 @@ void resample_host_tiles(const unsigned char* src, const dswx_resample_spec_t* s
                          int64_t stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out) {
     const int s = spec->shift;
     const size_t eb = F32 ? 4 : 2;
-    const int64_t mesh_w = ((dst_w + ((int64_t)1 << s) - 1) >> s) + 1;
+    const int64_t mesh_w = mesh_dims(dst_w, s);
     unsigned char* const dst = static_cast<unsigned char*>(out->dst);
     const uint32_t outside = spec->outside;              // (little endian: its low bytes come first)
     for (int64_t t = 0; t < n_tiles; ++t) {
@@ -269,7 +253,7 @@ void resample_host_tiles(const unsigned char* src, const dswx_resample_spec_t* s
         for (int64_t Y = 0; Y < dst_h; ++Y)
             for (int64_t X = 0; X < dst_w; ++X) {
                 int64_t sx, sy;
-                resample_position([&](int64_t k) { return res_mesh_at(mesh, m0 + k); }, s, mesh_w, X, Y, &sx, &sy);
+                mesh_position([&](int64_t k) { return mesh_node_at(mesh, m0 + k); }, s, mesh_w, X, Y, &sx, &sy);
                 const ResamplePixel px = resample_pixel(spec->method == DSWX_RESAMPLE_CUBIC, sx, sy, [&](int64_t c, int64_t r) {
                     if (c < 0 || c >= width || r < 0 || r >= height) return resample_no_tap();
                     uint32_t raw = 0;
@@ -304,7 +288,7 @@ int dswx_resample_host(const void* plane, const dswx_resample_spec_t* spec, int6
                        const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out) {
     int64_t stride;
     if (int rc = resample_check(plane, spec, n_tiles, height, width, mesh, dst_h, dst_w, out, &stride, false)) return rc;
-    if (dst_h == 0 || dst_w == 0 || !(out->dst || out->how || out->head)) return DSWX_OK;
+    if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->how || out->head)) return DSWX_OK;
     const unsigned char* const src = static_cast<const unsigned char*>(plane);
     if (spec->kind == DSWX_RESAMPLE_F32) resample_host_tiles<true>(src, spec, n_tiles, height, width, stride, mesh, dst_h, dst_w, out);
     else resample_host_tiles<false>(src, spec, n_tiles, height, width, stride, mesh, dst_h, dst_w, out);
@@ -317,39 +301,23 @@ int dswx_resample_device(dswx_ctx_t* ctx, const void* plane, const dswx_resample
     if (int rc = resample_check(plane, spec, n_tiles, height, width, mesh, dst_h, dst_w, out, &stride, true)) return rc;
     if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
-    if (n_tiles == 0 || dst_h == 0 || dst_w == 0 || !(out->dst || out->how || out->head)) {
+    if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->how || out->head)) {
         ctx->last_kernel = "none (empty input)";
         return DSWX_OK;
     }
     hipStream_t s = dswx_stream_of(ctx, stream);
     const bool f32 = spec->kind == DSWX_RESAMPLE_F32;
-    const unsigned long long nbx = ((unsigned long long)dst_w + RES_RECT_W - 1) / RES_RECT_W;
-    const unsigned long long nby = ((unsigned long long)dst_h + RES_RECT_H - 1) / RES_RECT_H;
     ResArgs a = {};
-    a.plane = static_cast<const unsigned char*>(plane);
-    a.src_stride_bytes = (unsigned long long)stride * (f32 ? 4u : 2u);
-    a.mesh = mesh;
-    a.mesh_stride_ints = 2ull * (unsigned long long)spec->mesh_tile_stride_nodes;
-    a.n_tiles = (unsigned long long)n_tiles;
-    a.n_rects = nbx * nby;
-    a.dst_px = (unsigned long long)dst_h * (unsigned long long)dst_w;
-    a.height = (int)height;
-    a.width = (int)width;
-    a.dst_h = (int)dst_h;
-    a.dst_w = (int)dst_w;
-    a.shift = spec->shift;
-    a.mesh_w = (int)((((long long)dst_w + (1LL << spec->shift) - 1) >> spec->shift) + 1);
+    unsigned gy;
+    if (int rc = dswx_mesh_launch_prepare(a, plane, stride, f32 ? 4 : 2, mesh, spec->mesh_tile_stride_nodes, spec->shift, n_tiles, height, width,
+                                          dst_h, dst_w, RES_RECT_H, RES_RECT_W, out->dst, out->head, s, &gy))
+        return rc;
     a.cubic = spec->method == DSWX_RESAMPLE_CUBIC;
     a.has_nodata = spec->has_nodata != 0;
     a.nodata = spec->nodata;
     a.outside = spec->outside;
-    a.nbx = (unsigned)nbx;
-    a.dst = static_cast<unsigned char*>(out->dst);
     a.how = out->how;
-    a.head = reinterpret_cast<unsigned long long*>(out->head);
-    if (out->head) HIP_TRY(hipMemsetAsync(out->head, 0xFF, (size_t)n_tiles * DSWX_RESAMPLE_HEAD_WORDS * sizeof(uint64_t), s));
     const unsigned gx = (unsigned)(a.n_rects < RES_MAX_GRID_X ? a.n_rects : RES_MAX_GRID_X);
-    const unsigned gy = (unsigned)(n_tiles < 65535 ? n_tiles : 65535);   // more tiles: the workgroups of a row of the grid walk them
     const dim3 grid(gx, gy), block(RES_BLOCK);
     if (f32) hipLaunchKernelGGL((dswx_resample_k<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((dswx_resample_k<false>), grid, block, 0, s, a);

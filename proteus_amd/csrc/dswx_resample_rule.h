@@ -1,8 +1,8 @@
 // dswx_resample_rule.h -- what the device kernel and the host statement of the resample (dswx_resample.hip; include/dswx_hip.h
-// "resample") share: the position of a destination pixel (the warp section's 64-bit integers, never restated in floating
-// point), the integer cubic weights, which tap is valid, the per-pixel rule in IEEE doubles and the rounding to the output
-// element.  Every product and every sum of the rule is ONE double operation rounded on its own: the build passes
-// -ffp-contract=off (proteus_amd/build.py) and nothing here may be fused, or device and host stop agreeing bit for bit.
+// "resample") share from the position of a destination pixel on (the position itself is dswx_mesh_rule.h): the integer cubic
+// weights, which tap is valid, the per-pixel rule in IEEE doubles and the rounding to the output element.  Every product and
+// every sum of the rule is ONE double operation rounded on its own: the build passes -ffp-contract=off (proteus_amd/build.py)
+// and nothing here may be fused, or device and host stop agreeing bit for bit.
 #pragma once
 
 #include <cmath>
@@ -21,24 +21,6 @@ namespace {
 #define DSWX_RESAMPLE_LDS_ELEMS 4096
 
 enum { RESAMPLE_OUTSIDE = 0, RESAMPLE_BILINEAR_FULL = 1, RESAMPLE_BILINEAR_RENORM = 2, RESAMPLE_CUBIC_FULL = 3 };
-
-// One coordinate of the position of destination pixel (X, Y) from the four nodes of its cell: include/dswx_hip.h "warp",
-// POSITION.  fx, fy < step = 1 << s, |v| <= 2^31, so |num| < 2^48.
-RESAMPLE_HD int64_t resample_coord(int64_t v00, int64_t v01, int64_t v10, int64_t v11, int64_t fx, int64_t fy, int s) {
-    const int64_t step = (int64_t)1 << s;
-    const int64_t num = (step - fy) * ((step - fx) * v00 + fx * v01) + fy * ((step - fx) * v10 + fx * v11);
-    return s ? (num + ((int64_t)1 << (2 * s - 1))) >> (2 * s) : num;
-}
-
-// The position (sx, sy) in 1/256 source pixel; node(k) returns int32 number k of the mesh of this tile (a load on the device,
-// an unaligned read on the host).
-template <class Node> RESAMPLE_HD void resample_position(Node node, int s, int64_t mesh_w, int64_t X, int64_t Y, int64_t* sx, int64_t* sy) {
-    const int64_t step = (int64_t)1 << s;
-    const int64_t i = Y >> s, fy = Y & (step - 1), j = X >> s, fx = X & (step - 1);
-    const int64_t n00 = 2 * (i * mesh_w + j), n10 = n00 + 2 * mesh_w;
-    *sx = resample_coord(node(n00), node(n00 + 2), node(n10), node(n10 + 2), fx, fy, s);
-    *sy = resample_coord(node(n00 + 1), node(n00 + 3), node(n10 + 1), node(n10 + 3), fx, fy, s);
-}
 
 // Keys' cubic, a = -0.5 (Catmull-Rom), at f / 256: integers over 2^25 that sum to 2^25, each of magnitude <= 2^25.
 RESAMPLE_HD void resample_weights(int f, double* n) {

@@ -8,9 +8,9 @@
 // the grid take several).  One wave owns each row; a thread owns WARP_PPT = 16 consecutive destination pixels of its row, a
 // unit, which never straddles a destination row.  The last unit of a row (dst_w % 16 pixels) is stored element by element.
 //
-// POSITIONS.  Within one mesh cell the numerator of the definition is linear in fx: num = A + fx * B with
-//     A = (step - fy) * step * x[i][j] + fy * step * x[i+1][j],   B = (step - fy) * (x[i][j+1] - x[i][j]) + fy * (x[i+1][j+1] - x[i+1][j])
-// in 64-bit integers (|A|, |fx * B| < 2^48: the same exact integers as the definition's products, in another order).  With
+// POSITIONS.  dswx_mesh_rule.h states them: the definition (mesh_position: dswx_warp_host below and the resample entries) and
+// the form this kernel uses, the definition's numerator within one mesh cell, num = A + fx * B in 64-bit integers
+// (mesh_cell_linear); tests/native/mesh_host_san.cpp runs both on the host and holds them equal over whole cells.  With
 // shift >= 4 the unit of a thread lies in ONE cell (its first column is a multiple of 16 and so is the step): the thread reads
 // the four nodes once -- 32 bytes that four to sixteen neighbouring threads share through the caches -- and advances the two
 // numerators by B per pixel; the rounding shift and the floor to a pixel are one 64-bit arithmetic shift by 2 * shift + 8.
@@ -81,14 +81,9 @@ __device__ __forceinline__ void warp_cell(const int* mesh, long long node, int m
     const u32x2 n01 = *reinterpret_cast<const u32x2_w*>(mesh + 2 * (node + 1));
     const u32x2 n10 = *reinterpret_cast<const u32x2_w*>(mesh + 2 * (node + mesh_w));
     const u32x2 n11 = *reinterpret_cast<const u32x2_w*>(mesh + 2 * (node + mesh_w + 1));
-    // 32 x 32 -> 64 bit products (the weights are at most 256, the nodes int32), and a shift for the factor `step`
     const int gy = (int)(step - fy), hy = (int)fy, s = __builtin_ctzll((unsigned long long)step);
-    const int x00 = (int)n00[0], x01 = (int)n01[0], x10 = (int)n10[0], x11 = (int)n11[0];
-    const int y00 = (int)n00[1], y01 = (int)n01[1], y10 = (int)n10[1], y11 = (int)n11[1];
-    ax = ((long long)gy * x00 + (long long)hy * x10) << s;
-    bx = (long long)gy * x01 - (long long)gy * x00 + (long long)hy * x11 - (long long)hy * x10;
-    ay = ((long long)gy * y00 + (long long)hy * y10) << s;
-    by = (long long)gy * y01 - (long long)gy * y00 + (long long)hy * y11 - (long long)hy * y10;
+    mesh_cell_linear((int)n00[0], (int)n01[0], (int)n10[0], (int)n11[0], gy, hy, s, ax, bx);
+    mesh_cell_linear((int)n00[1], (int)n01[1], (int)n10[1], (int)n11[1], gy, hy, s, ay, by);
 }
 
 template <int EB> __device__ __forceinline__ uint32_t warp_load(const unsigned char* src, uint32_t idx) {
@@ -327,11 +322,6 @@ __global__ __launch_bounds__(WARP_BLOCK) void dswx_warp_k(const WarpArgs a) {
 }
 
 // unaligned host accesses (a host buffer may sit at any address)
-inline int64_t mesh_at(const int32_t* base, int64_t i) {
-    int32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
-}
 template <typename T> inline void put_at(void* base, int64_t i, T v) {
     std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * sizeof(T), &v, sizeof(T));
 }
@@ -354,8 +344,7 @@ int dswx_mesh_geometry_check(int shift, int reserved, int64_t src_tile_stride, i
     const int64_t n_elems = height * width;
     *src_stride = src_tile_stride ? src_tile_stride : n_elems;
     if (*src_stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "src_tile_stride smaller than the tile");
-    const int64_t step = 1LL << shift;
-    const int64_t mesh_h = ((dst_h + step - 1) >> shift) + 1, mesh_w = ((dst_w + step - 1) >> shift) + 1;
+    const int64_t mesh_h = mesh_dims(dst_h, shift), mesh_w = mesh_dims(dst_w, shift);
     if (mesh_tile_stride_nodes && mesh_tile_stride_nodes < mesh_h * mesh_w)
         return dswx_fail(DSWX_ERR_ARG, "mesh_tile_stride_nodes %lld smaller than the mesh (%lld x %lld nodes)",
                          (long long)mesh_tile_stride_nodes, (long long)mesh_h, (long long)mesh_w);
@@ -364,6 +353,20 @@ int dswx_mesh_geometry_check(int shift, int reserved, int64_t src_tile_stride, i
         return dswx_fail(DSWX_ERR_ARG, "plane too large");
     if (mesh_tile_stride_nodes > (1LL << 46) || (n_tiles && (uint64_t)mesh_tile_stride_nodes > (1ull << 46) / (uint64_t)n_tiles))
         return dswx_fail(DSWX_ERR_ARG, "mesh too large");
+    return DSWX_OK;
+}
+
+int dswx_mesh_pointer_check(bool work, const void* plane, bool plane_read, int elem_bytes, const int32_t* mesh, const void* dst,
+                            const uint32_t* src_index, const uint64_t* head, bool align) {
+    if (work && !mesh) return dswx_fail(DSWX_ERR_ARG, "mesh is NULL");
+    if (work && !plane && plane_read) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
+    if (align) {
+        if (!aligned_to(mesh, 4)) return dswx_fail(DSWX_ERR_ALIGN, "mesh not 4-byte aligned");
+        if (!aligned_to(src_index, 4)) return dswx_fail(DSWX_ERR_ALIGN, "src_index not 4-byte aligned");
+        if (!aligned_to(head, 8)) return dswx_fail(DSWX_ERR_ALIGN, "head not 8-byte aligned");
+        if (!aligned_to(plane, (size_t)elem_bytes)) return dswx_fail(DSWX_ERR_ALIGN, "plane not %d-byte aligned", elem_bytes);
+        if (!aligned_to(dst, (size_t)elem_bytes)) return dswx_fail(DSWX_ERR_ALIGN, "dst not %d-byte aligned", elem_bytes);
+    }
     return DSWX_OK;
 }
 
@@ -378,55 +381,28 @@ int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_t
     if (int rc = dswx_mesh_geometry_check(spec->shift, spec->reserved, spec->src_tile_stride, spec->mesh_tile_stride_nodes, n_tiles, height,
                                           width, dst_h, dst_w, src_stride))
         return rc;
-    const int64_t n_elems = height * width;
-    const bool work = n_tiles > 0 && dst_h > 0 && dst_w > 0 && (out->dst || out->src_index || out->head);
-    if (work && !mesh) return dswx_fail(DSWX_ERR_ARG, "mesh is NULL");
-    if (work && !plane && n_elems > 0 && out->dst) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
-    if (align) {
-        if (!aligned_to(mesh, 4)) return dswx_fail(DSWX_ERR_ALIGN, "mesh not 4-byte aligned");
-        if (!aligned_to(out->src_index, 4)) return dswx_fail(DSWX_ERR_ALIGN, "src_index not 4-byte aligned");
-        if (!aligned_to(out->head, 8)) return dswx_fail(DSWX_ERR_ALIGN, "head not 8-byte aligned");
-        if (!aligned_to(plane, (size_t)spec->elem_bytes)) return dswx_fail(DSWX_ERR_ALIGN, "plane not %d-byte aligned", spec->elem_bytes);
-        if (!aligned_to(out->dst, (size_t)spec->elem_bytes)) return dswx_fail(DSWX_ERR_ALIGN, "dst not %d-byte aligned", spec->elem_bytes);
-    }
-    return DSWX_OK;
+    const bool work = dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->src_index || out->head);
+    return dswx_mesh_pointer_check(work, plane, height * width > 0 && out->dst, spec->elem_bytes, mesh, out->dst, out->src_index, out->head, align);
 }
 
 // One memset (of `head`, if wanted) and one launch; the arguments have passed dswx_warp_check, `src_stride` is the resolved
 // stride of the plane in elements (a batch has its own).
 int dswx_warp_launch(dswx_ctx* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                      int64_t src_stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, hipStream_t s) {
-    if (n_tiles == 0 || dst_h == 0 || dst_w == 0 || !(out->dst || out->src_index || out->head)) {
+    if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->src_index || out->head)) {
         ctx->last_kernel = "none (empty input)";
         return DSWX_OK;
     }
     const int eb = spec->elem_bytes;
-    const unsigned long long nbx = ((unsigned long long)dst_w + WARP_COLS - 1) / WARP_COLS;
-    const unsigned long long nby = ((unsigned long long)dst_h + WARP_ROWS - 1) / WARP_ROWS;
     WarpArgs a = {};
-    a.plane = static_cast<const unsigned char*>(plane);
-    a.src_stride_bytes = (unsigned long long)src_stride * (unsigned)eb;
-    a.mesh = mesh;
-    a.mesh_stride_ints = 2ull * (unsigned long long)spec->mesh_tile_stride_nodes;
-    a.n_tiles = (unsigned long long)n_tiles;
-    a.n_rects = nbx * nby;
-    a.dst_px = (unsigned long long)dst_h * (unsigned long long)dst_w;
-    a.height = (int)height;
-    a.width = (int)width;
-    a.dst_h = (int)dst_h;
-    a.dst_w = (int)dst_w;
-    a.shift = spec->shift;
-    a.mesh_w = (int)((((long long)dst_w + (1LL << spec->shift) - 1) >> spec->shift) + 1);
+    unsigned gy;
+    if (int rc = dswx_mesh_launch_prepare(a, plane, src_stride, eb, mesh, spec->mesh_tile_stride_nodes, spec->shift, n_tiles, height, width,
+                                          dst_h, dst_w, WARP_ROWS, WARP_COLS, out->dst, out->head, s, &gy))
+        return rc;
     a.outside = spec->outside;
     a.thin = height < (1 << 23) && width < (1 << 23);
-    a.nbx = (unsigned)nbx;
-    a.dst = static_cast<unsigned char*>(out->dst);
     a.src_index = out->src_index;
-    a.head = reinterpret_cast<unsigned long long*>(out->head);
-    if (out->head) HIP_TRY(hipMemsetAsync(out->head, 0xFF, (size_t)n_tiles * DSWX_WARP_HEAD_WORDS * sizeof(uint64_t), s));
     const unsigned gx = (unsigned)(a.n_rects < WARP_MAX_GRID_X ? a.n_rects : WARP_MAX_GRID_X);
-    // more than 65535 tiles: the workgroups of a row of the grid walk the tiles
-    const unsigned gy = (unsigned)(n_tiles < 65535 ? n_tiles : 65535);
     const dim3 grid(gx, gy), block(WARP_BLOCK);
     const bool fine = spec->shift < 4;
     if (eb == 1 && fine) hipLaunchKernelGGL((dswx_warp_k<1, true>), grid, block, 0, s, a);
@@ -449,10 +425,9 @@ int dswx_warp_host(const void* plane, const dswx_warp_spec_t* spec, int64_t n_ti
                    const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out) {
     int64_t stride;
     if (int rc = dswx_warp_check(plane, spec, n_tiles, height, width, mesh, dst_h, dst_w, out, &stride, false)) return rc;
-    if (dst_h == 0 || dst_w == 0 || !(out->dst || out->src_index || out->head)) return DSWX_OK;
+    if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->src_index || out->head)) return DSWX_OK;
     const int s = spec->shift, eb = spec->elem_bytes;
-    const int64_t step = 1LL << s, half = s ? 1LL << (2 * s - 1) : 0;
-    const int64_t mesh_w = ((dst_w + step - 1) >> s) + 1;
+    const int64_t mesh_w = mesh_dims(dst_w, s);
     const unsigned char* const src = static_cast<const unsigned char*>(plane);
     unsigned char* const dst = static_cast<unsigned char*>(out->dst);
     const uint32_t outside = spec->outside;              // (little endian: its low elem_bytes bytes come first)
@@ -462,15 +437,9 @@ int dswx_warp_host(const void* plane, const dswx_warp_spec_t* spec, int64_t n_ti
         int64_t rmin = height, rmax = 0, cmin = width, cmax = 0;
         for (int64_t Y = 0; Y < dst_h; ++Y)
             for (int64_t X = 0; X < dst_w; ++X) {
-                const int64_t i = Y >> s, fy = Y & (step - 1), j = X >> s, fx = X & (step - 1);
-                int64_t pos[2];
-                for (int k = 0; k < 2; ++k) {
-                    const int64_t v00 = mesh_at(mesh, m0 + 2 * (i * mesh_w + j) + k), v01 = mesh_at(mesh, m0 + 2 * (i * mesh_w + j + 1) + k);
-                    const int64_t v10 = mesh_at(mesh, m0 + 2 * ((i + 1) * mesh_w + j) + k), v11 = mesh_at(mesh, m0 + 2 * ((i + 1) * mesh_w + j + 1) + k);
-                    const int64_t num = (step - fy) * ((step - fx) * v00 + fx * v01) + fy * ((step - fx) * v10 + fx * v11);
-                    pos[k] = (num + half) >> (2 * s);
-                }
-                const int64_t c = pos[0] >> 8, r = pos[1] >> 8;
+                int64_t sx, sy;
+                mesh_position([&](int64_t k) { return mesh_node_at(mesh, m0 + k); }, s, mesh_w, X, Y, &sx, &sy);
+                const int64_t c = sx >> 8, r = sy >> 8;
                 const bool in = c >= 0 && c < width && r >= 0 && r < height;
                 const int64_t e = t * dst_h * dst_w + Y * dst_w + X;
                 if (dst) std::memcpy(dst + (size_t)e * eb, in ? src + ((size_t)t * (size_t)stride + (size_t)(r * width + c)) * eb

@@ -164,24 +164,30 @@ class DevicePlane:
         from . import warp as _warp
         if len(self.shape) not in (2, 3) or self.dtype.itemsize not in (1, 2, 4):
             raise ValueError(f'a warp is made of a [n, H, W] or [H, W] plane of 1-, 2- or 4-byte elements, not {self.dtype} {self.shape}')
+        return self._through_mesh('warp', mesh, dst_shape, shift, want, _capi._warp_planes, _capi.WarpOut,
+                                  lambda stride: _warp.Spec(self.dtype.itemsize, shift, outside, mesh_tile_stride_nodes=stride))
+
+    def _through_mesh(self, what, mesh, dst_shape, shift, want, planes, out_type, make_spec):
+        """What `warp` and `resample` share: the destination and the mesh validated, the spec made by make_spec(nodes between
+        the meshes of consecutive tiles), the mesh uploaded for the one call of self.engine.ctx.<what>_device and released."""
+        from .warp import mesh_shape
         n_tiles = self.shape[0] if len(self.shape) == 3 else 1
         height, width = self.shape[-2:]
         shape = tuple(int(v) for v in dst_shape)
         if len(shape) != 2 or min(shape) < 0 or shape[0] * shape[1] > _capi.WARP_MAX_PIXELS:
             raise ValueError(f'a destination is (dst_h, dst_w) of at most {_capi.WARP_MAX_PIXELS} pixels, not {dst_shape}')
-        mh, mw = _warp.mesh_shape(shape, shift)
+        mh, mw = mesh_shape(shape, shift)
         mesh = np.ascontiguousarray(mesh, dtype=np.int32)
         if mesh.shape not in ((mh, mw, 2), (n_tiles, mh, mw, 2)):
             raise ValueError(f'a mesh for {shape} at shift {shift} is [{mh}, {mw}, 2] or [{n_tiles}, {mh}, {mw}, 2], not {mesh.shape}')
-        spec = _warp.Spec(self.dtype.itemsize, shift, outside, mesh_tile_stride_nodes=mh * mw if mesh.ndim == 4 else 0)
+        spec = make_spec(mh * mw if mesh.ndim == 4 else 0)
         lead = (n_tiles,) if len(self.shape) == 3 else ()
-        made = _capi._warp_planes(want, self.dtype, n_tiles, shape,
-                                  lambda shp, dt: self.engine.plane(shp if len(shp) == 2 else lead + tuple(shp[1:]), dt))
-        out = _capi.WarpOut.of(**{k: p.ptr for k, p in made.items()})
+        made = planes(want, self.dtype, n_tiles, shape, lambda shp, dt: self.engine.plane(shp if len(shp) == 2 else lead + tuple(shp[1:]), dt))
+        out = out_type.of(**{k: p.ptr for k, p in made.items()})
         table = self.engine.upload(mesh)
         try:
-            with self.engine.lock, stages.span('gpu: warp'):
-                self.engine.ctx.warp_device(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
+            with self.engine.lock, stages.span(f'gpu: {what}'):
+                getattr(self.engine.ctx, f'{what}_device')(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
                 self.engine.ctx.synchronize()
         finally:
             table.release()
@@ -195,31 +201,11 @@ class DevicePlane:
         tap (resample.outside_word).  A dict of DevicePlanes for the outputs named in `want` -- 'dst' [n, dst_h, dst_w] of this
         plane's dtype ([dst_h, dst_w] for one raster), 'how' uint8 of the same shape, 'head' uint64 [n, 8] -- which stay on the
         device: the DEM of a product run goes on to the shadow kernel."""
-        from . import resample as _resample, warp as _warp
+        from . import resample as _resample
         if len(self.shape) not in (2, 3):
             raise ValueError(f'a resample is made of a [n, H, W] or [H, W] plane, not {self.shape}')
-        n_tiles = self.shape[0] if len(self.shape) == 3 else 1
-        height, width = self.shape[-2:]
-        shape = tuple(int(v) for v in dst_shape)
-        if len(shape) != 2 or min(shape) < 0 or shape[0] * shape[1] > _capi.WARP_MAX_PIXELS:
-            raise ValueError(f'a destination is (dst_h, dst_w) of at most {_capi.WARP_MAX_PIXELS} pixels, not {dst_shape}')
-        mh, mw = _warp.mesh_shape(shape, shift)
-        mesh = np.ascontiguousarray(mesh, dtype=np.int32)
-        if mesh.shape not in ((mh, mw, 2), (n_tiles, mh, mw, 2)):
-            raise ValueError(f'a mesh for {shape} at shift {shift} is [{mh}, {mw}, 2] or [{n_tiles}, {mh}, {mw}, 2], not {mesh.shape}')
-        spec = _resample.Spec(self.dtype, method, shift, nodata, outside, mesh_tile_stride_nodes=mh * mw if mesh.ndim == 4 else 0)
-        lead = (n_tiles,) if len(self.shape) == 3 else ()
-        made = _capi._resample_planes(want, self.dtype, n_tiles, shape,
-                                      lambda shp, dt: self.engine.plane(shp if len(shp) == 2 else lead + tuple(shp[1:]), dt))
-        out = _capi.ResampleOut.of(**{k: p.ptr for k, p in made.items()})
-        table = self.engine.upload(mesh)
-        try:
-            with self.engine.lock, stages.span('gpu: resample'):
-                self.engine.ctx.resample_device(self.ptr, spec, n_tiles, height, width, table.ptr, shape[0], shape[1], out)
-                self.engine.ctx.synchronize()
-        finally:
-            table.release()
-        return made
+        return self._through_mesh('resample', mesh, dst_shape, shift, want, _capi._resample_planes, _capi.ResampleOut,
+                                  lambda stride: _resample.Spec(self.dtype, method, shift, nodata, outside, mesh_tile_stride_nodes=stride))
 
     def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
         """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;

@@ -418,6 +418,22 @@ def test_every_refusal_needs_no_device_and_writes_nothing():
         resample_tiles(np.zeros((1, 2, 2), dtype=np.uint8), mesh, 2, (DH, DW), CUBIC)
 
 
+def test_host_binding_refuses_a_mesh_with_too_few_nodes():
+    """As tests/test_warp.py has it for the warp: the binding knows the mesh array's size and refuses one with fewer nodes than
+    the destination needs, before dswx_resample_host would read past its end."""
+    src = np.zeros((2, 3, 4), dtype=np.float32)
+    mh, mw = mesh_shape((5, 9), 2)
+    mesh = np.zeros((2, mh * mw + 1, 2), dtype=np.int32)
+    per_tile = Spec(np.float32, CUBIC, 2, mesh_tile_stride_nodes=mh * mw + 1)
+    assert _capi.resample_host(src, mesh[0, :mh * mw], Spec(np.float32, CUBIC, 2), (5, 9))['dst'].shape == (2, 5, 9)      # exactly enough
+    assert _capi.resample_host(src, mesh.reshape(-1, 2)[:-1], per_tile, (5, 9))['dst'].shape == (2, 5, 9)             # (the last tile has no padding)
+    with pytest.raises(ValueError, match='too small'):
+        _capi.resample_host(src, mesh[0, :mh * mw - 1], Spec(np.float32, CUBIC, 2), (5, 9))
+    with pytest.raises(ValueError, match='too small'):
+        _capi.resample_host(src, mesh.reshape(-1, 2)[:-2], per_tile, (5, 9))
+    assert _capi.resample_host(src, mesh[0, :1], Spec(np.float32, CUBIC, 2), (0, 9))['head'].tolist() == [[0] * 8] * 2  # nothing to read
+
+
 def test_header_says_has_resample_and_the_struct_mirrors_match(tmp_path):
     import shutil
     import subprocess

@@ -315,6 +315,55 @@ def test_every_refusal_needs_no_device_and_writes_nothing():
         Spec(1, 9)
 
 
+def test_host_binding_refuses_a_mesh_with_too_few_nodes():
+    """dswx_warp_host trusts the caller's mesh to have mesh_h * mesh_w nodes per tile; the binding knows the array's size and
+    refuses a smaller one before the call would read past its end."""
+    src = np.zeros((2, 3, 4), dtype=np.uint8)
+    mh, mw = mesh_shape((5, 9), 2)
+    mesh = np.zeros((2, mh * mw + 1, 2), dtype=np.int32)
+    per_tile = Spec(1, 2, 9, mesh_tile_stride_nodes=mh * mw + 1)
+    assert _capi.warp_host(src, mesh[0, :mh * mw], Spec(1, 2, 9), (5, 9))['dst'].shape == (2, 5, 9)         # exactly enough
+    assert _capi.warp_host(src, mesh.reshape(-1, 2)[:-1], per_tile, (5, 9))['dst'].shape == (2, 5, 9)       # (the last tile has no padding)
+    with pytest.raises(ValueError, match='too small'):
+        _capi.warp_host(src, mesh[0, :mh * mw - 1], Spec(1, 2, 9), (5, 9))
+    with pytest.raises(ValueError, match='too small'):
+        _capi.warp_host(src, mesh.reshape(-1, 2)[:-2], per_tile, (5, 9))
+    assert _capi.warp_host(src, mesh[0, :1], Spec(1, 2, 9), (0, 9))['head'].tolist() == [[0] * 8] * 2      # nothing to read
+
+
+def test_mesh_rule_and_host_entries_under_asan_and_ubsan_in_a_program_of_their_own():
+    """tests/native/mesh_host_san.cpp with proteus_amd/csrc/dswx_warp.hip and dswx_resample.hip compiled into it, host code
+    under ASan + UBSan: the warp kernel's per-cell linear form (dswx_mesh_rule.h, executed on the host) against the definition
+    for every fx and fy of a cell at every shift with nodes up to INT32_MIN and INT32_MAX, the definition against 128-bit
+    integers, and both host entries on heap blocks of exactly the bytes they may touch at odd addresses, every result against
+    a plain loop.  A child process; nothing is loaded into this interpreter."""
+    import json
+    import shutil
+    import subprocess
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        pytest.skip('needs hipcc')
+    out_dir = os.path.join(ROOT, 'tests', 'native', '_build')
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, 'mesh_host_san')
+    csrc = os.path.join(ROOT, 'proteus_amd', 'csrc')
+    cmd = [hipcc, '--offload-arch=gfx950', '-std=c++17', '-g', '-O1', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
+           '-Xarch_host', '-fsanitize=address,undefined', '-Xarch_host', '-fno-sanitize-recover=undefined',
+           '-I', os.path.join(ROOT, 'include'), '-I', csrc,
+           os.path.join(ROOT, 'tests', 'native', 'mesh_host_san.cpp'), os.path.join(csrc, 'dswx_warp.hip'), os.path.join(csrc, 'dswx_resample.hip'),
+           '-o', exe]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if res.returncode != 0 and 'libclang_rt.asan' in res.stderr:     # (only the runtime: an error in the sources must fail)
+        pytest.skip(f'sanitizer runtime missing: {res.stderr[-300:]}')
+    assert res.returncode == 0, res.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:halt_on_error=1', UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1')
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, (res.stdout[-1000:], res.stderr[-4000:])
+    assert 'ERROR: AddressSanitizer' not in res.stderr and 'runtime error' not in res.stderr and 'LeakSanitizer' not in res.stderr
+    out = json.loads(res.stdout.strip().splitlines()[-1])
+    assert out['failures'] == 0 and out['cases'] >= 100
+
+
 def test_header_says_has_warp_and_the_struct_mirrors_match(tmp_path):
     import shutil
     import subprocess
