@@ -23,6 +23,8 @@ from proteus_amd import _capi, geotiff, warp
 from proteus_amd.warp import OUTSIDE, Spec, mesh_shape, warp_tiles
 from proteus_amd.synth import SEED
 from tests.test_warp import DSTS, MESHES, OUT_WORD, SHIFTS, SRCS, exact_mesh, make_mesh, random_tiles
+from tests.test_warp import (DTYPES, ENTER_K, ENTER_SLOPES, FLAT_DST, LONG_SIDE, WALK_SRCS, affine_mesh, check_traits, decimation_cases,
+                             entering_cases, fit_offsets, flat_cases, long_side_cases, outside_of, slope_cases, switch_cases, whole_units)
 
 pytestmark = pytest.mark.gpu
 
@@ -223,6 +225,146 @@ def test_a_raster_side_of_2_to_the_23_leaves_the_32_bit_arithmetic(ctx):
             ref = run_device(ctx, bufs, tiles, make_mesh('rotation', (33, 300), 4, (4, 600), rng), Spec(1, 4, OUT_WORD), (33, 300), what=(src, 'rotation'))
     finally:
         bufs.free()
+
+
+# ---- the position walk: every slope, sign and edge (the cases and their conditions: tests/test_warp.py, pinned there on the host) --
+
+def run_cases(ctx, cases, eb, seed):
+    """Every case through run_device on two tiles -- every byte of dst, src_index and head against dswx_warp_host -- and the
+    conditions that make the case worth running, on the reference that the device has just been held to."""
+    rng = np.random.default_rng(seed)
+    bufs, planes, count = Bufs(ctx), {}, 0
+    try:
+        for case in cases:
+            key = case['src']
+            if key not in planes:
+                planes[key] = random_tiles(rng, 1 if key[0] * key[1] > 1 << 20 else 2, key, eb)
+            ref = run_device(ctx, bufs, planes[key], case['mesh'], Spec(eb, case['shift'], OUT_WORD), case['dst'], off=1 + 2 * (count % 2),
+                             what=(case['name'], case['shift'], case['src']))
+            check_traits(case, ref)
+            count += 1
+    finally:
+        bufs.free()
+    return count
+
+
+@pytest.mark.parametrize('shift', (4, 6, 8))
+@pytest.mark.parametrize('eb', (1, 2, 4))
+def test_slopes_and_signs_on_the_32_bit_path(ctx, shift, eb):
+    """Section (a) of tests/test_warp.py slope_cases on rasters of 100 x 257 and 300 x 470: the column, then the row, running
+    along a destination row at +-85 .. +-1023 / 256 pixels per pixel (repeated pixels, flips, units inside that are no runs,
+    transposes and quarter turns), shears that change the source row inside a unit, rotations by 30 .. 183 degrees; every
+    destination hangs over two opposite edges of the raster, so fractions and pixels go negative under the rounding shift.
+    unit_paths infers the 32-bit form for every unit of every case."""
+    assert run_cases(ctx, (c for src in WALK_SRCS for c in slope_cases(shift, src)), eb, 4800 + 10 * shift + eb) == 94
+    assert 'fine=0' in ctx.last_kernel_info()
+
+
+@pytest.mark.parametrize('eb', (1, 2, 4))
+def test_the_switch_between_the_forms_at_four_pixels(ctx, eb):
+    """Section (b): node differences one below, on and one above four source pixels per destination pixel, in x, in y, in both,
+    negated; and cells whose two edges lie either side of it, so that units of both forms are neighbours in one launch."""
+    assert run_cases(ctx, (c for s in (4, 8) for c in switch_cases(s, WALK_SRCS[1])), eb, 4810 + eb) == 48
+
+
+@pytest.mark.parametrize('eb', (1, 2, 4))
+def test_entering_the_raster_from_outside_and_the_clamp(ctx, eb):
+    """Section (c): units whose first pixel lies 1 .. 200 pixels outside each of the four edges and that walk towards the raster
+    at 1, 2 and 3.99 pixels per pixel -- either side of the 60 pixels a unit can cover and of the -128 that the kernel clamps
+    its first pixel to -- and units 2^22 pixels away."""
+    assert run_cases(ctx, entering_cases(WALK_SRCS[0]), eb, 4820 + eb) == 4 * len(ENTER_K) * len(ENTER_SLOPES) + 8
+
+
+@pytest.mark.parametrize('eb', (1, 2, 4))
+def test_a_run_across_a_rows_end_and_off_the_end_of_the_tile(ctx, eb):
+    """Section (d): at shift 0 every node is the centre of the source pixel with the same flat index, so every unit is 16
+    consecutive elements and one load, also where it runs from a row's end into the next row's start; moved on by 7 and by 16
+    elements the last units run off the end of the tile and are the `outside` word, not the first elements of the next tile
+    (tile 0) nor the bytes behind the plane (tile 1).  At shift 3 the same nodes on a source 8 wide: exact positions, no run
+    (tests/test_warp.py flat_cases says why)."""
+    rng = np.random.default_rng(4830 + eb)
+    bufs = Bufs(ctx)
+    fill = outside_of(DTYPES[eb])
+    n = FLAT_DST[0] * FLAT_DST[1]
+    try:
+        for case in flat_cases():
+            tiles = random_tiles(rng, 2, case['src'], eb)
+            tiles[tiles == fill] ^= 1                                         # no element is the `outside` word
+            ref = run_device(ctx, bufs, tiles, case['mesh'], Spec(eb, case['shift'], OUT_WORD), case['dst'], off=3, what=case['name'])
+            check_traits(case, ref)
+            move = case['name'][2]
+            flat, dst, idx = tiles.reshape(2, -1), ref['dst'].reshape(2, -1), ref['src_index'].reshape(2, -1)
+            if case['shift'] == 0:
+                assert np.array_equal(dst[:, :n - move], flat[:, move:]) and np.array_equal(idx[:, :n - move], np.tile(np.arange(move, n), (2, 1)))
+                assert np.all(dst[:, n - move:] == fill) and np.all(idx[:, n - move:] == OUTSIDE), case['name']
+            else:
+                assert np.array_equal(dst[idx != OUTSIDE], flat[:, case['flat'][case['flat'] < n]].reshape(-1)) and np.all(dst[idx == OUTSIDE] == fill)
+            assert 'fine=1' in ctx.last_kernel_info()
+    finally:
+        bufs.free()
+
+
+def test_the_64_bit_form_at_the_far_end_of_a_long_raster(ctx):
+    """Section (e) on the rasters of 2 x 2^23 and 2^23 x 2: the walk along the long side at -1, 2, 3 and 3.99 pixels per pixel
+    up to the last node that int32 can hold, the short side entered and left."""
+    assert run_cases(ctx, (c for src in ((2, LONG_SIDE), (LONG_SIDE, 2)) for c in long_side_cases(src)), 1, 4840) == 8
+
+
+@pytest.mark.parametrize('eb', (1, 2, 4))
+def test_decimation_by_4_5_and_16_takes_the_64_bit_form(ctx, eb):
+    """Section (e) on a raster of 300 x 470: +-4, +-5 and +-16 pixels per pixel along a row, in the column and in the row."""
+    assert run_cases(ctx, (c for s in (4, 8) for c in decimation_cases(s, WALK_SRCS[1])), eb, 4850 + eb) == 24
+
+
+@pytest.mark.parametrize('eb', (1, 4))
+def test_slopes_and_signs_where_every_pixel_has_its_own_cell(ctx, eb):
+    """Section (f): the cases of (a) at shifts 0 and 3 (the FINE instantiation) on the raster of 100 x 257."""
+    assert run_cases(ctx, (c for s in (0, 3) for c in slope_cases(s, WALK_SRCS[0])), eb, 4860 + eb) == 94
+    assert 'fine=1' in ctx.last_kernel_info()
+
+
+def test_a_flip_and_a_decimation_behind_the_batch_and_the_plane(ctx):
+    """Section (g): a mesh of slope -1 and one of slope 2 through dswx_batch_warp on the WTR and the NIR plane against
+    dswx_warp_host, and through DevicePlane.warp against warp_tiles."""
+    from proteus_amd.pipeline import TileEngine
+    n_tiles, h, w, dst, shift = 3, 61, 67, (70, 90), 4
+    meshes = {}
+    for name, xs, ys in (('flip', (-256, 0), (0, 256)), ('half', (512, 0), (0, 512))):
+        cx, cy = fit_offsets(dst, xs, ys, (h, w))
+        meshes[name] = affine_mesh(dst, shift, xs + (cx,), ys + (cy,))
+    batch = _capi.DeviceBatch(ctx, n_tiles, h, w)
+    mbuf = ctx.malloc(meshes['flip'].nbytes)
+    eng = TileEngine(ctx)
+    try:
+        batch.synth(SEED, tile0=47)
+        batch.classify(_capi.default_params())
+        for plane, dtype in (('wtr', np.uint8), ('nir', np.int16)):
+            tiles = np.stack([batch.read_tile(plane, t) for t in range(n_tiles)]).reshape(n_tiles, h, w)
+            assert tiles.dtype == dtype and len(np.unique(tiles)) > 1
+            resident = eng.upload(tiles)
+            for name, mesh in meshes.items():
+                spec = Spec(tiles.dtype.itemsize, shift, OUT_WORD)
+                want = _capi.warp_host(tiles, mesh, spec, dst)
+                assert 0.1 < int(want['head'][0, 1]) / int(want['head'][0, 0]) < 0.9
+                if name == 'flip':
+                    idx, inside = whole_units(want['src_index'][0], dst)
+                    assert (inside.all(axis=2) & np.all(np.diff(idx, axis=2) == -1, axis=2)).any()
+                mbuf.upload(mesh.view(np.uint8).reshape(-1))
+                res = batch.warp(plane, mbuf.ptr, dst, spec)
+                info = ctx.last_kernel_info()
+                ctx.synchronize()
+                got = download(res, dtype, n_tiles, dst)
+                assert info.count('dswx_warp_k') == 1 and f'elem_bytes={spec.elem_bytes}' in info, info
+                for k in KEYS:
+                    assert np.array_equal(got[k], want[k].reshape(-1)), (plane, name, k)
+                res = resident.warp(mesh, dst, shift, outside=OUT_WORD, want=KEYS)
+                ref = warp_tiles(tiles, mesh, shift, dst, OUT_WORD)
+                for k in KEYS:
+                    assert np.array_equal(res[k].numpy(), ref[k]) and np.array_equal(ref[k], want[k]), (plane, name, k)
+    finally:
+        eng.close()
+        mbuf.free()
+        batch.free()
 
 
 def test_on_a_callers_stream_behind_the_copy_that_writes_the_plane(ctx):

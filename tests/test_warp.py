@@ -392,6 +392,400 @@ def test_header_says_has_warp_and_the_struct_mirrors_match(tmp_path):
     assert got['words'] == f'{_capi.WARP_HEAD_WORDS} shift {_capi.WARP_MAX_SHIFT} outside {_capi.WARP_OUTSIDE}' and _capi.WARP_HEAD_WORDS == 8
 
 
+# ---- the position walk of the kernel: meshes of every slope, sign and edge ---------------------------------------------------
+# The builders, the cases and their conditions live here, where the host entry is pinned on them (no GPU needed);
+# tests/test_gpu_warp.py runs the same cases through dswx_warp_device against the host entry.
+
+UNIT = 16                                                    # destination pixels per thread of dswx_warp_k (_capi.WARP_UNIT)
+SLOPES = (85, 102, 256, 384, 512, 640, 768, 1021, 1023)      # 1/256 source pixel per destination pixel, all below four pixels
+DECIMATIONS = (1024, 1280, 4096)                             # four pixels and more: the 64-bit form
+ROTATIONS = (30, 45, 87, 177, 183)
+WALK_SRCS = ((100, 257), (300, 470))
+ENTER_K = (1, 15, 16, 59, 60, 61, 127, 128, 129, 130, 200)
+ENTER_SLOPES = (256, 512, 1021)
+FAR = 1 << 22                                                # source pixels: nodes near 2^30
+
+
+def affine_mesh(dst, shift, xc, yc):
+    """The mesh whose node for destination pixel (X, Y) is (ax * X + bx * Y + cx, ay * X + by * Y + cy), xc = (ax, bx, cx) and
+    yc = (ay, by, cy) integers in 1/256 source pixel (per destination pixel): fractional slopes are exact, and so is every
+    interpolated position, a bilinear mesh being exact on an affine function."""
+    mh, mw = mesh_shape(dst, shift)
+    step = 1 << shift
+    X, Y = np.meshgrid(np.arange(mw, dtype=np.int64) * step, np.arange(mh, dtype=np.int64) * step)
+    nodes = np.stack([int(xc[0]) * X + int(xc[1]) * Y + int(xc[2]), int(yc[0]) * X + int(yc[1]) * Y + int(yc[2])], axis=-1)
+    assert nodes.min() >= INT32_MIN and nodes.max() <= INT32_MAX, (xc, yc)
+    return nodes.astype(np.int32)
+
+
+def rotation_mesh(dst, shift, src, degrees, scale=1.0):
+    """make_mesh('rotation') with the angle as a parameter: the middle of the destination on the middle of the source, turned by
+    `degrees` and magnified by `scale` source pixels per destination pixel."""
+    mh, mw = mesh_shape(dst, shift)
+    step = 1 << shift
+    jj, ii = np.meshgrid(np.arange(mw, dtype=np.int64) * step, np.arange(mh, dtype=np.int64) * step)
+    a = math.radians(degrees)
+    dx, dy = 256 * jj + 128 - 128.0 * dst[1], 256 * ii + 128 - 128.0 * dst[0]
+    x = np.rint(128.0 * src[1] + scale * (math.cos(a) * dx - math.sin(a) * dy)).astype(np.int64)
+    y = np.rint(128.0 * src[0] + scale * (math.sin(a) * dx + math.cos(a) * dy)).astype(np.int64)
+    return np.stack([x, y], axis=-1).astype(np.int32)
+
+
+def unit_paths(mesh, shift, dst, src):
+    """bool [dst_h, ceil(dst_w / 16)]: the unit of 16 destination pixels takes the narrow (32-bit) form of dswx_warp_k -- by the
+    kernel's statement of its rule: both sides of the raster below 2^23 and |bx|, |by| < 1 << (2 * shift + 10), with b recomputed
+    here in int64 from the four nodes of the unit's cell as dswx_mesh_rule.h states it, gy * (v01 - v00) + hy * (v11 - v10),
+    gy = step - fy, hy = fy.  Shift >= 4 only: a unit lies in one cell.  This INFERS the path; nothing the device does is
+    observed, so a kernel that took the other form with the same bits would pass.  What is observed is that the units of both
+    kinds give the host entry's bits."""
+    assert shift >= 4
+    dh, dw = dst
+    m = np.asarray(mesh).astype(np.int64)
+    assert m.shape == mesh_shape(dst, shift) + (2,)
+    step = 1 << shift
+    Y, X = np.arange(dh, dtype=np.int64)[:, None], np.arange(0, dw, UNIT, dtype=np.int64)[None, :]
+    i, fy, j = Y >> shift, Y & (step - 1), X >> shift
+    lim = 1 << (2 * shift + 10)
+    narrow = np.full((dh, X.shape[1]), src[0] < (1 << 23) and src[1] < (1 << 23))
+    for k in range(2):
+        v = m[:, :, k]
+        b = (step - fy) * (v[i, j + 1] - v[i, j]) + fy * (v[i + 1, j + 1] - v[i + 1, j])
+        narrow &= np.abs(b) < lim
+    return narrow
+
+
+def whole_units(index, dst):
+    """int64 [dst_h, dst_w // 16, 16]: the source indices of the whole units of one tile, and which of them lie inside."""
+    u = np.asarray(index).reshape(dst)[:, :dst[1] // UNIT * UNIT].reshape(dst[0], -1, UNIT)
+    return u.astype(np.int64), u != OUTSIDE
+
+
+def fit_offsets(dst, xs, ys, src):
+    """(cx, cy) for the linear parts xs = (ax, bx), ys = (ay, by): a coordinate whose extent over the destination is 1.25 sides
+    of the raster or more is centred on it and hangs over both edges; a shorter one lies with a fifth of its extent in front of
+    the first row or column, where positions are negative.  An odd number of 1/256 is added: no position is a pixel's centre."""
+    out = []
+    for (a, b), side, odd in ((xs, src[1], 37), (ys, src[0], 91)):
+        ends = [a * X + b * Y for X in (0, dst[1] - 1) for Y in (0, dst[0] - 1)]
+        lo, hi = min(ends), max(ends)
+        out.append((128 * side - (lo + hi) // 2 if hi - lo >= 320 * side else -lo - (hi - lo) // 5) + odd)
+    return out
+
+
+def axis_slice(o, m, n, size):
+    """(slice of the destination, slice of the source) along one axis for source coordinate o + m * k of destination
+    coordinate k < n, m != 0: where that lies inside 0 .. size - 1; None where none does."""
+    v = o + m * np.arange(n)
+    ok = np.flatnonzero((v >= 0) & (v < size))
+    if not len(ok):
+        return None
+    k0, k1 = int(ok[0]), int(ok[-1]) + 1
+    assert len(ok) == k1 - k0
+    stop = int(v[k1 - 1]) + (1 if m > 0 else -1)
+    return slice(k0, k1), slice(int(v[k0]), stop if stop >= 0 else None, m)
+
+
+def closed_form(case, tiles, fill):
+    """`dst` of a case whose coefficients are whole pixels, by numpy slices: family 'x' is src[:, oy + q * Y, ox + m * X] -- a
+    slice, [::-1] and [::p, ::p] in one -- and family 'y' the transpose of src[:, oy + m * X, ox + q * Y]."""
+    fam, m, q, ox, oy = case['whole']
+    dh, dw = case['dst']
+    H, W = case['src']
+    want = np.full((len(tiles), dh, dw), fill, dtype=tiles.dtype)
+    if fam == 'x':
+        rows, cols = axis_slice(oy, q, dh, H), axis_slice(ox, m, dw, W)
+        if rows and cols:
+            want[:, rows[0], cols[0]] = tiles[:, rows[1], cols[1]]
+    else:
+        rows, cols = axis_slice(oy, m, dw, H), axis_slice(ox, q, dh, W)
+        if rows and cols:
+            want[:, cols[0], rows[0]] = tiles[:, rows[1], cols[1]].transpose(0, 2, 1)
+    return want
+
+
+def axis_case(fam, slope, shift, src, dst_h=21):
+    """One coordinate runs along the destination's rows at `slope` (family 'x': the column, 'y': the row, the column standing
+    still: transposes and quarter turns), the other along its columns in whole pixels, 1.3 sides of the raster over the
+    destination's height.  The destination is as wide as 1.5 sides of the raster take at this slope, between 53 and 293."""
+    along, across = (src[1], src[0]) if fam == 'x' else (src[0], src[1])
+    dw = min(max(-(-384 * along // abs(slope)), 48), 288) // UNIT * UNIT + 5
+    dst = (dst_h, dw)
+    q = 256 * -(-14 * across // (10 * dst_h))
+    xs, ys = ((slope, 0), (0, q)) if fam == 'x' else ((0, q), (slope, 0))
+    cx, cy = fit_offsets(dst, xs, ys, src)
+    traits = ['share', 'narrow' if abs(slope) < 1024 else 'wide']
+    if abs(slope) < 256:
+        traits.append('repeats')
+    if slope == 256:
+        traits.append('runs and cuts' if fam == 'x' else 'no run')
+    if slope == -256:
+        traits.append('descends by 1' if fam == 'x' else 'descends by a row')
+    case = dict(name=(fam, slope), shift=shift, src=src, dst=dst, mesh=affine_mesh(dst, shift, xs + (cx,), ys + (cy,)), traits=traits)
+    if slope % 256 == 0:
+        case['whole'] = (fam, slope // 256, q // 256, cx >> 8, cy >> 8)
+    return case
+
+
+def slope_cases(shift, src, slopes=SLOPES, bent=True):
+    """Section (a): both families at every slope and sign; with `bent`, the shears x = X + 0.3 Y with y = Y + 0.25 X, each sign
+    flipped in turn, on a destination of 9 rows that hangs over the raster's left and right edges, and the rotations, magnified
+    until the destination's long side is 1.3 widths of the raster."""
+    for fam in 'xy':
+        for slope in slopes:
+            for sign in (1, -1):
+                yield axis_case(fam, sign * slope, shift, src)
+    if not bent:
+        return
+    dst = (9, (1024 if src[1] < 300 else 2048) + 17)
+    for xs, ys in (((256, 77), (64, 256)), ((-256, 77), (64, 256)), ((256, -77), (64, 256)), ((256, 77), (-64, 256)), ((256, 77), (64, -256)),
+                   ((-256, -77), (-64, -256))):
+        cx, cy = fit_offsets(dst, xs, ys, src)
+        # the rows that the columns inside the raster take: around the raster's middle
+        cy = 128 * src[0] - (ys[0] * (128 * src[1] - cx) // xs[0] + ys[1] * (dst[0] // 2)) + 91
+        yield dict(name=('shear', xs, ys), shift=shift, src=src, dst=dst, mesh=affine_mesh(dst, shift, xs + (cx,), ys + (cy,)), traits=['share', 'narrow'])
+    dst = (70, 300)
+    for deg in ROTATIONS:
+        yield dict(name=('rotation', deg), shift=shift, src=src, dst=dst, mesh=rotation_mesh(dst, shift, src, deg, 1.3 * src[1] / dst[1]),
+                   traits=['share', 'narrow'])
+
+
+def decimation_cases(shift, src):
+    """Section (e) on an ordinary raster: slopes of 4, 5 and 16 pixels, both signs and families: every unit in the 64-bit form."""
+    return slope_cases(shift, src, DECIMATIONS, bent=False)
+
+
+def switch_cases(shift, src):
+    """Section (b): meshes built from node DIFFERENCES along a row around lim = 4 * 256 * step, the difference at which
+    b = step * (v01 - v00) reaches 1 << (2 * shift + 10): lim - 1 (narrow), lim and lim + 1 (wide; the comparison is strict), in
+    x only, in y only, in both, and negated.  The twisted meshes have lim - 16 on one edge of every cell and lim + 16 on the
+    other, alternating along both axes of the mesh, so b = lim +- 16 * (2 fy - step) crosses the limit at the middle row of a
+    cell.  A destination has at most 70 rows: at shift 4 (70 x 300) the crossing lies between the rows of every cell; at shift 8
+    its row 128 cannot, and the destination is 9 x 2065, where neighbouring cells of the row of cells lie on either side."""
+    step = 1 << shift
+    lim = 4 * 256 * step
+    for twisted in (False, True):
+        dst = (9, 2 * 1024 + 17) if twisted and shift == 8 else (70, 300)
+        mh, mw = mesh_shape(dst, shift)
+        i, j = np.meshgrid(np.arange(mh, dtype=np.int64), np.arange(mw - 1, dtype=np.int64), indexing='ij')
+        for delta in ((16,) if twisted else (-1, 0, 1)):
+            d = lim - delta * (1 - 2 * ((i + j) & 1)) if twisted else lim + delta + 0 * i      # [mh, mw - 1] differences along the rows
+            for where in ('x', 'y', 'both'):
+                for sign in (1, -1):
+                    nodes = np.zeros((mh, mw, 2), dtype=np.int64)
+                    for k, side in ((0, src[1]), (1, src[0])):
+                        if where in ('xy'[k], 'both'):
+                            walk = np.concatenate([np.zeros((mh, 1), dtype=np.int64), np.cumsum(sign * d, axis=1)], axis=1)
+                            span = lim * (dst[1] // step + 1)
+                            nodes[:, :, k] = walk + (-(span // 5) if sign > 0 else 256 * side + span // 5) + 41
+                            if where == 'both' and k == 1:
+                                nodes[:, :, k] += 256 * step * np.arange(mh, dtype=np.int64)[:, None]
+                        else:                                                                 # a pixel per destination row, from row or column 3
+                            nodes[:, :, k] = (256 * step * np.arange(mh, dtype=np.int64) + 256 * 3 + 128)[:, None]
+                    assert nodes.min() >= INT32_MIN and nodes.max() <= INT32_MAX
+                    traits = ['some inside', 'both sides' if twisted else ('narrow' if delta < 0 else 'wide')]
+                    if twisted and shift == 4:
+                        traits.append('crosses inside cells')
+                    yield dict(name=('switch', 'twisted' if twisted else delta, where, sign), shift=shift, src=src, dst=dst,
+                               mesh=nodes.astype(np.int32), traits=traits)
+
+
+def entering_cases(src):
+    """Section (c), shift 4: the first pixel of the first unit of every row lies k source pixels before the left edge and the
+    row walks into the raster at the slope; the same before the top edge with the slope in y, and mirrored past the right and
+    the bottom edge with the slope negated; the other coordinate is three pixels inside.  The kernel clamps the unit's first
+    pixel to -128 (k >= 129).  And translations by 2^22 source pixels either way: nodes near +-2^30."""
+    H, W = src
+    dst, still = (5, 14 * UNIT + 5), (0, 256, 256 * 3 + 128)
+    for slope in ENTER_SLOPES:
+        for k in ENTER_K:
+            traits = ['some inside'] + (['first unit enters'] if k <= 59 and slope == 1021 else []) + (['first unit outside'] if k >= 128 else [])
+            yield dict(name=('left', slope, k), shift=4, src=src, dst=dst, traits=traits, mesh=affine_mesh(dst, 4, (slope, 0, -256 * k + 128), still))
+            yield dict(name=('right', slope, k), shift=4, src=src, dst=dst, traits=traits,
+                       mesh=affine_mesh(dst, 4, (-slope, 0, 256 * (W - 1 + k) + 128), still))
+            yield dict(name=('top', slope, k), shift=4, src=src, dst=dst, traits=traits, mesh=affine_mesh(dst, 4, still, (slope, 0, -256 * k + 128)))
+            yield dict(name=('bottom', slope, k), shift=4, src=src, dst=dst, traits=traits,
+                       mesh=affine_mesh(dst, 4, still, (-slope, 0, 256 * (H - 1 + k) + 128)))
+    for slope in (256, 768):
+        for far in (256 * FAR, -256 * FAR):
+            yield dict(name=('far x', slope, far), shift=4, src=src, dst=dst, traits=['nothing inside'], mesh=affine_mesh(dst, 4, (slope, 0, far + 128), still))
+            yield dict(name=('far y', slope, far), shift=4, src=src, dst=dst, traits=['nothing inside'], mesh=affine_mesh(dst, 4, still, (slope, 0, far + 128)))
+
+
+def flat_mesh(dst, shift, src_w, move):
+    """Every node is the centre of the source pixel (of a raster `src_w` wide) whose flat index is that of the node's
+    destination pixel plus `move`."""
+    mh, mw = mesh_shape(dst, shift)
+    step = 1 << shift
+    X, Y = np.meshgrid(np.arange(mw, dtype=np.int64) * step, np.arange(mh, dtype=np.int64) * step)
+    f = Y * dst[1] + X + move
+    return np.stack([256 * (f % src_w) + 128, 256 * (f // src_w) + 128], axis=-1).astype(np.int32)
+
+
+FLAT_DST, FLAT_MOVES = (20, 48), (0, 7, 16)
+
+
+def flat_cases():
+    """Section (d).  Shift 0, a source of 24 x 40 and a destination of 20 x 48: every unit is 16 consecutive elements, one of
+    every five across a row's end (two with an odd move); moved on by 7 and by 16 elements the last units run off the end of the tile.
+    Shift 3 with a source 8 wide (120 x 8): every node has the same column (48 and the step are multiples of 8) and its row is
+    linear in X and Y, so the interpolated positions are exact -- column `move`, row (f + 4) >> 3 of the pixel with flat index
+    f -- but NOT consecutive: the positions of a mesh are continuous across its nodes, so at a shift above 0 the column cannot
+    fall back by a row's width between two pixels, and a run across a row's end exists at shift 0 alone."""
+    n = FLAT_DST[0] * FLAT_DST[1]
+    for move in FLAT_MOVES:
+        want = np.arange(n, dtype=np.int64) + move
+        yield dict(name=('flat', 0, move), shift=0, src=(24, 40), dst=FLAT_DST, mesh=flat_mesh(FLAT_DST, 0, 40, move), traits=['flat'], flat=want)
+        want = 8 * ((np.arange(n, dtype=np.int64) + 4) >> 3) + move
+        yield dict(name=('flat', 3, move), shift=3, src=(120, 8), dst=FLAT_DST, mesh=flat_mesh(FLAT_DST, 3, 8, move), traits=['flat'], flat=want)
+
+
+LONG_SIDE = 1 << 23
+LONG_DST = (33, 300)
+
+
+def long_side_cases(src):
+    """Section (e) on the rasters of 2 x 2^23 and 2^23 x 2: the slope along the long side, the last node of a row (or the
+    first, for the negative slope) 50 / 256 of a pixel in front of INT32_MAX, the end of the raster; the short side takes 8
+    destination rows per pixel from one pixel outside."""
+    long_x = src[1] == LONG_SIDE
+    assert src in ((2, LONG_SIDE), (LONG_SIDE, 2))
+    last = (mesh_shape(LONG_DST, 4)[1] - 1) * 16
+    for slope in (-256, 512, 768, 1021):
+        along = (slope, 0, INT32_MAX - 50 - max(slope, 0) * last)
+        short = (0, 32, -256)
+        yield dict(name=('long side', src, slope), shift=4, src=src, dst=LONG_DST, traits=['some inside', 'wide'],
+                   mesh=affine_mesh(LONG_DST, 4, along, short) if long_x else affine_mesh(LONG_DST, 4, short, along))
+
+
+def check_traits(case, ref):
+    """What makes a case worth running, asserted on the reference's outputs of its first tile: conditions, not measurements."""
+    head, dst, src, shift = ref['head'][0], case['dst'], case['src'], case['shift']
+    name = case['name']
+    idx, inside = whole_units(ref['src_index'][0], dst)
+    whole = inside.all(axis=2)
+    step = np.diff(idx, axis=2)
+    for trait in case['traits']:
+        if trait == 'share':
+            assert 0.1 < int(head[1]) / int(head[0]) < 0.9, (name, head[:3])
+        elif trait == 'some inside':
+            assert 0 < head[1] < head[0], (name, head[:3])
+        elif trait == 'nothing inside':
+            assert head[1] == 0, (name, head[:3])
+        elif trait in ('narrow', 'wide', 'both sides', 'crosses inside cells'):
+            if shift < 4:
+                continue                                                     # (the FINE instantiation has one form)
+            narrow = unit_paths(case['mesh'], shift, dst, src)
+            if trait == 'narrow':
+                assert narrow.all(), name
+            elif trait == 'wide':
+                assert not narrow.any(), name
+            elif trait == 'both sides':
+                assert 0.25 <= narrow.mean() <= 0.75, (name, narrow.mean())
+            else:
+                cells = narrow[:dst[0] >> shift << shift].reshape(dst[0] >> shift, 1 << shift, -1)
+                assert (cells.any(axis=1) & ~cells.all(axis=1)).all(), name
+        elif trait == 'repeats':
+            assert ((step == 0) & inside[:, :, 1:] & inside[:, :, :-1]).any(), name
+        elif trait == 'runs and cuts':
+            runs = whole & np.all(step == 1, axis=2)
+            assert runs.any() and (~runs).any(), name
+        elif trait == 'no run':
+            assert not (whole & np.all(step == 1, axis=2)).any() and (whole & np.all(step == src[1], axis=2)).any(), name
+        elif trait == 'descends by 1':
+            assert (whole & np.all(step == -1, axis=2)).any(), name
+        elif trait == 'descends by a row':
+            assert (whole & np.all(step == -src[1], axis=2)).any(), name
+        elif trait == 'first unit enters':
+            assert inside[:, 0, :].any(), name
+        elif trait == 'first unit outside':
+            assert not inside[:, 0, :].any(), name
+        elif trait == 'flat':
+            want = np.where(case['flat'] < src[0] * src[1], case['flat'], OUTSIDE)
+            assert np.array_equal(ref['src_index'][0].reshape(-1), want), name
+            if shift == 0:                                                   # whole units across a source row's end
+                assert (whole & np.all(step == 1, axis=2) & (idx[:, :, 0] // src[1] != idx[:, :, -1] // src[1])).sum() >= 10, name
+        else:
+            raise AssertionError(trait)
+
+
+def pin_on_the_host(case, rng, planes, n=2):
+    """dswx_warp_host on a case against the loop in Python ints and warp_tiles, every output and element size; its closed form;
+    its conditions."""
+    shift, src, dst, mesh = case['shift'], case['src'], case['dst'], case['mesh']
+    pos = loop_positions(mesh, shift, dst)
+    sx, sy = warp.positions(mesh, shift, dst)
+    assert [p[0] for p in pos] == sx.reshape(-1).tolist() and [p[1] for p in pos] == sy.reshape(-1).tolist(), case['name']
+    ebs = (1,) if src[0] * src[1] > 1 << 20 else (1, 2, 4)
+    for eb in ebs:
+        if (src, eb) not in planes:                                          # one plane per raster and element size
+            planes[src, eb] = random_tiles(rng, 1 if len(ebs) == 1 else n, src, eb)
+        tiles = planes[src, eb]
+        fill = outside_of(tiles.dtype)
+        got = _capi.warp_host(tiles, mesh, Spec(eb, shift, OUT_WORD), dst)
+        ref = warp_tiles(tiles, mesh, shift, dst, OUT_WORD)
+        for k in warp.OUTPUTS:
+            assert got[k].dtype == ref[k].dtype and np.array_equal(got[k], ref[k]), (case['name'], eb, k)
+        if len(ebs) == 1:                                                    # (a raster of 2^24 elements is not made a list)
+            c, r = np.array([p[0] >> 8 for p in pos]), np.array([p[1] >> 8 for p in pos])
+            ok = (c >= 0) & (c < src[1]) & (r >= 0) & (r < src[0])
+            idx = np.where(ok, r * src[1] + c, OUTSIDE)
+            assert np.array_equal(got['src_index'][0].reshape(-1), idx) and got['head'][0, 1] == ok.sum()
+            assert np.array_equal(got['dst'][0].reshape(-1)[ok], tiles[0].reshape(-1)[idx[ok]]) and np.all(got['dst'][0].reshape(-1)[~ok] == fill)
+        else:
+            t = eb % n
+            d, idx, head = loop_warp(tiles[t], pos, dst, fill)
+            assert np.array_equal(got['dst'][t], d) and np.array_equal(got['src_index'][t], idx) and np.array_equal(got['head'][t], head), (case['name'], eb)
+        if 'whole' in case:
+            assert np.array_equal(got['dst'], closed_form(case, tiles, fill)), (case['name'], eb, 'closed form')
+        if 'flat' in case and case['shift'] == 0 and case['name'][2] == 0:
+            assert np.array_equal(got['dst'], tiles.reshape((-1,) + dst))
+    check_traits(case, got)
+
+
+WALK_SECTIONS = {
+    'slopes at shift 4': lambda: (c for src in WALK_SRCS for c in slope_cases(4, src)),
+    'slopes at shift 6': lambda: (c for src in WALK_SRCS for c in slope_cases(6, src)),
+    'slopes at shift 8': lambda: (c for src in WALK_SRCS for c in slope_cases(8, src)),
+    'fine':lambda: (c for s in (0, 3) for c in slope_cases(s, WALK_SRCS[0])),
+    'switch': lambda: (c for s in (4, 8) for c in switch_cases(s, WALK_SRCS[1])),
+    'entering': lambda: entering_cases(WALK_SRCS[0]),
+    'flat': flat_cases,
+    'decimation': lambda: (c for s in (4, 8) for c in decimation_cases(s, WALK_SRCS[1])),
+    'long side': lambda: (c for src in ((2, LONG_SIDE), (LONG_SIDE, 2)) for c in long_side_cases(src)),
+}
+
+
+@pytest.mark.parametrize('section', list(WALK_SECTIONS))
+def test_the_meshes_of_the_position_walk_on_the_host(section):
+    """Every mesh that tests/test_gpu_warp.py drives the kernel's position walk with, at its sizes, through dswx_warp_host: equal
+    to the loop in Python ints and to warp_tiles on every output, to numpy slices where the coefficients are whole pixels, and
+    with every condition that makes the case worth running on the device."""
+    rng = np.random.default_rng(7000 + len(section))
+    count, planes = 0, {}
+    for case in WALK_SECTIONS[section]():
+        pin_on_the_host(case, rng, planes)
+        count += 1
+    assert count >= 6, count
+
+
+def test_unit_paths_and_the_builders_say_what_they_claim():
+    """affine_mesh is the node formula; unit_paths follows the raster's sides, the limit of four pixels and its strictness."""
+    m = affine_mesh((5, 9), 2, (3, -7, 11), (-256, 1023, -5))
+    assert m.shape == (3, 4, 2) and m[2, 3].tolist() == [3 * 12 - 7 * 8 + 11, -256 * 12 + 1023 * 8 - 5]
+    sx, sy = warp.positions(m, 2, (5, 9))
+    assert sx[4, 7] == 3 * 7 - 7 * 4 + 11 and sy[3, 8] == -256 * 8 + 1023 * 3 - 5
+    dst = (20, 40)
+    for shift in (4, 8):
+        lim = 4 * 256 << shift
+        for d, narrow in ((lim - 1, True), (lim, False), (1 - lim, True), (-lim, False)):
+            mesh = np.zeros(mesh_shape(dst, shift) + (2,), dtype=np.int64)
+            mesh[:, :, 1] = d * np.arange(mesh.shape[1])
+            assert unit_paths(mesh, shift, dst, (100, 100)).shape == (20, 3)
+            assert unit_paths(mesh, shift, dst, (100, 100)).all() == narrow and unit_paths(mesh, shift, dst, (100, 100)).any() == narrow
+            assert not unit_paths(mesh, shift, dst, (1 << 23, 2)).any() and not unit_paths(mesh, shift, dst, (2, 1 << 23)).any()
+            assert unit_paths(mesh, shift, dst, ((1 << 23) - 1, 2)).all() == narrow
+
+
 # ---- the projection, pinned without PROJ ---------------------------------------------------------------------------------
 
 A, F, K0 = warp.WGS84_A, 1.0 / warp.WGS84_INV_F, warp.UTM_K0
