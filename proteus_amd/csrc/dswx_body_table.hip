@@ -473,20 +473,6 @@ __global__ __launch_bounds__(BODY_BLOCK) void dswx_body_fill_k(const BodyArgs a)
     }
 }
 
-// unaligned host accesses (a host buffer may sit at any address)
-inline uint32_t get_u32(const uint32_t* base, int64_t i) {
-    uint32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
-}
-inline void put_u32(uint32_t* base, int64_t i, uint32_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 4, &v, 4); }
-inline uint64_t get_u64(const uint32_t* base, int64_t word) {
-    uint64_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)word * 4, 8);
-    return v;
-}
-inline void put_u64(void* base, int64_t byte, uint64_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)byte, &v, 8); }
-
 }  // namespace
 
 // The checks that the device and the host entry share, in the house order: the arguments before any context, nothing
@@ -503,13 +489,11 @@ int dswx_body_check(const uint32_t* label, const uint8_t* value, const dswx_body
     if (height > BODY_MAX_PIXELS || width > BODY_MAX_PIXELS || height * width > BODY_MAX_PIXELS)
         return dswx_fail(DSWX_ERR_ARG, "raster too large: height * width above 2^31, a label would not fit 32 bits");
     const int64_t n_elems = height * width;
-    if (*stride == 0) *stride = n_elems;
-    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "value_stride smaller than the tile");
-    if (n_tiles > (1LL << 32) || *stride > (1LL << 46) || (n_tiles && (uint64_t)*stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
+    if (int rc = dswx_tile_stride_check(stride, n_elems, "value_stride")) return rc;
+    if (int rc = dswx_tile_extent_check(*stride, n_tiles, true)) return rc;
     if (spec->max_rows > BODY_MAX_ROWS) return dswx_fail(DSWX_ERR_ARG, "max_rows %lld above 2^31", (long long)spec->max_rows);
     if (!out->dense) return dswx_fail(DSWX_ERR_ARG, "dense is NULL: it is the working array and always required");
-    if (!label && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "label is NULL");
+    if (int rc = dswx_tile_plane_check(label, n_tiles, n_elems, "label")) return rc;
     if (!out->rows && spec->max_rows > 0) return dswx_fail(DSWX_ERR_ARG, "rows is NULL with max_rows %lld", (long long)spec->max_rows);
     if (align) {
         if (!aligned_to(label, 4)) return dswx_fail(DSWX_ERR_ALIGN, "label not 4-byte aligned");
@@ -524,7 +508,7 @@ int dswx_body_check(const uint32_t* label, const uint8_t* value, const dswx_body
 int dswx_body_launch(dswx_ctx* ctx, const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
                      int64_t height, int64_t width, int64_t stride, const dswx_body_out_t* out, hipStream_t s) {
     if (n_tiles == 0 || height == 0 || width == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     BodyArgs a = {};
@@ -579,14 +563,14 @@ int dswx_body_table_host(const uint32_t* label, const uint8_t* value, const dswx
         // the roots in rising order: their ranks, and the beginning of their rows
         uint64_t k = 0;
         for (int64_t p = 0; p < n; ++p) {
-            const bool root = body_is_root(get_u32(lab, p), (uint64_t)p);
-            put_u32(den, p, root ? (uint32_t)(k + 1) : 0u);
+            const bool root = body_is_root(dswx_load<uint32_t>(lab, p), (uint64_t)p);
+            dswx_store<uint32_t>(den, p, root ? (uint32_t)(k + 1) : 0u);
             if (!root) continue;
             if (rows && (int64_t)k < max_rows) {
                 uint32_t* row = rows + (size_t)k * DSWX_BODY_ROW_WORDS;
-                put_u32(row, BODY_LABEL, (uint32_t)p + 1u);
-                put_u32(row, BODY_X_MIN, 0xFFFFFFFFu);
-                put_u32(row, BODY_Y_MIN, (uint32_t)(p / width));
+                dswx_store<uint32_t>(row, BODY_LABEL, (uint32_t)p + 1u);
+                dswx_store<uint32_t>(row, BODY_X_MIN, 0xFFFFFFFFu);
+                dswx_store<uint32_t>(row, BODY_Y_MIN, (uint32_t)(p / width));
             }
             ++k;
         }
@@ -595,36 +579,36 @@ int dswx_body_table_host(const uint32_t* label, const uint8_t* value, const dswx
         for (int64_t y = 0; y < height; ++y)
             for (int64_t x = 0; x < width; ++x) {
                 const int64_t p = y * width + x;
-                const uint32_t L = get_u32(lab, p);
+                const uint32_t L = dswx_load<uint32_t>(lab, p);
                 if (!L) continue;
                 uint32_t dv = 0;
-                if (body_in_reach(L, (uint64_t)p) && get_u32(lab, (int64_t)L - 1) == L) dv = get_u32(den, (int64_t)L - 1);
-                put_u32(den, p, dv);
+                if (body_in_reach(L, (uint64_t)p) && dswx_load<uint32_t>(lab, (int64_t)L - 1) == L) dv = dswx_load<uint32_t>(den, (int64_t)L - 1);
+                dswx_store<uint32_t>(den, p, dv);
                 if (!dv) {
                     ++bad;
                     continue;
                 }
                 ++good;
-                const uint32_t e = (x == 0 || get_u32(lab, p - 1) != L ? 1u : 0u) + (x == width - 1 || get_u32(lab, p + 1) != L ? 1u : 0u) +
-                                   (y == 0 || get_u32(lab, p - width) != L ? 1u : 0u) + (y == height - 1 || get_u32(lab, p + width) != L ? 1u : 0u);
+                const uint32_t e = (x == 0 || dswx_load<uint32_t>(lab, p - 1) != L ? 1u : 0u) + (x == width - 1 || dswx_load<uint32_t>(lab, p + 1) != L ? 1u : 0u) +
+                                   (y == 0 || dswx_load<uint32_t>(lab, p - width) != L ? 1u : 0u) + (y == height - 1 || dswx_load<uint32_t>(lab, p + width) != L ? 1u : 0u);
                 edges += e;
                 if (!rows || (int64_t)dv - 1 >= max_rows) continue;
                 uint32_t* row = rows + (size_t)(dv - 1u) * DSWX_BODY_ROW_WORDS;
-                put_u32(row, BODY_AREA, get_u32(row, BODY_AREA) + 1u);
-                if ((uint32_t)x < get_u32(row, BODY_X_MIN)) put_u32(row, BODY_X_MIN, (uint32_t)x);
-                if ((uint32_t)x > get_u32(row, BODY_X_MAX)) put_u32(row, BODY_X_MAX, (uint32_t)x);
-                if ((uint32_t)y > get_u32(row, BODY_Y_MAX)) put_u32(row, BODY_Y_MAX, (uint32_t)y);
-                put_u64(row, BODY_PERIMETER * 4, get_u64(row, BODY_PERIMETER) + e);
-                put_u64(row, BODY_SUM_X * 4, get_u64(row, BODY_SUM_X) + (uint64_t)x);
-                put_u64(row, BODY_SUM_Y * 4, get_u64(row, BODY_SUM_Y) + (uint64_t)y);
+                dswx_store<uint32_t>(row, BODY_AREA, dswx_load<uint32_t>(row, BODY_AREA) + 1u);
+                if ((uint32_t)x < dswx_load<uint32_t>(row, BODY_X_MIN)) dswx_store<uint32_t>(row, BODY_X_MIN, (uint32_t)x);
+                if ((uint32_t)x > dswx_load<uint32_t>(row, BODY_X_MAX)) dswx_store<uint32_t>(row, BODY_X_MAX, (uint32_t)x);
+                if ((uint32_t)y > dswx_load<uint32_t>(row, BODY_Y_MAX)) dswx_store<uint32_t>(row, BODY_Y_MAX, (uint32_t)y);
+                dswx_store<uint64_t>(row + BODY_PERIMETER, 0, dswx_load<uint64_t>(row + BODY_PERIMETER, 0) + e);
+                dswx_store<uint64_t>(row + BODY_SUM_X, 0, dswx_load<uint64_t>(row + BODY_SUM_X, 0) + (uint64_t)x);
+                dswx_store<uint64_t>(row + BODY_SUM_Y, 0, dswx_load<uint64_t>(row + BODY_SUM_Y, 0) + (uint64_t)y);
                 if (val) {
                     const unsigned c = body_cat(spec->cat_of_byte[val[p]], spec->n_cats);
-                    if (c != BODY_NOT_COUNTED) put_u32(row, BODY_COUNT + (int64_t)c, get_u32(row, BODY_COUNT + (int64_t)c) + 1u);
+                    if (c != BODY_NOT_COUNTED) dswx_store<uint32_t>(row, BODY_COUNT + (int64_t)c, dswx_load<uint32_t>(row, BODY_COUNT + (int64_t)c) + 1u);
                 }
             }
         if (out->head) {
             const uint64_t head[DSWX_BODY_HEAD_WORDS] = {k, k < (uint64_t)max_rows ? k : (uint64_t)max_rows, good, bad, edges, 0, 0, 0};
-            for (int w = 0; w < DSWX_BODY_HEAD_WORDS; ++w) put_u64(out->head, (t * DSWX_BODY_HEAD_WORDS + w) * 8, head[w]);
+            for (int w = 0; w < DSWX_BODY_HEAD_WORDS; ++w) dswx_store<uint64_t>(out->head, (size_t)(t * DSWX_BODY_HEAD_WORDS + w), head[w]);
         }
     }
     return DSWX_OK;
@@ -633,9 +617,7 @@ int dswx_body_table_host(const uint32_t* label, const uint8_t* value, const dswx
 int dswx_body_table_device(dswx_ctx_t* ctx, const uint32_t* label, const uint8_t* value, const dswx_body_spec_t* spec, int64_t n_tiles,
                            int64_t height, int64_t width, int64_t stride, const dswx_body_out_t* out, void* stream) {
     if (int rc = dswx_body_check(label, value, spec, n_tiles, height, width, &stride, out, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_body_launch(ctx, label, value, spec, n_tiles, height, width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_body_launch(ctx, label, value, spec, n_tiles, height, width, stride, out, s); });
 }
 
 }  // extern "C"

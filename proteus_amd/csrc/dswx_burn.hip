@@ -249,19 +249,6 @@ __global__ __launch_bounds__(BURN_BLOCK) void dswx_burn_scan_k(const BurnArgs a)
     burn_flush_inside(a, t, &inside, lane);              // (t may be n_tiles here: nothing is left to add then)
 }
 
-// unaligned host accesses (a host buffer may sit at any address)
-inline int64_t get_i64(const void* base, size_t index) {
-    int64_t v;
-    std::memcpy(&v, static_cast<const unsigned char*>(base) + index * 8, 8);
-    return v;
-}
-inline dswx_burn_vertex_t get_vertex(const void* base, size_t index) {
-    dswx_burn_vertex_t v;
-    std::memcpy(&v, static_cast<const unsigned char*>(base) + index * 16, 16);
-    return v;
-}
-inline void put_u64(void* base, size_t index, uint64_t v) { std::memcpy(static_cast<unsigned char*>(base) + index * 8, &v, 8); }
-
 }  // namespace
 
 // The checks that the entries share, in the house order: the arguments before any context, nothing written by a refused call.
@@ -300,7 +287,7 @@ int dswx_burn_check(const void* verts, const int64_t* tile_first, const dswx_bur
 int dswx_burn_launch(dswx_ctx* ctx, const void* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, const uint8_t* src, int64_t mask_stride, int64_t src_stride, const dswx_burn_out_t* out, hipStream_t s) {
     if (n_tiles == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     BurnArgs a = {};
@@ -345,16 +332,16 @@ int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, c
     const int64_t n = height * width;
     std::vector<uint32_t> acc((size_t)n);
     for (int64_t t = 0; t < n_tiles; ++t) {
-        const int64_t first = get_i64(tile_first, (size_t)t), count = burn_count(first, get_i64(tile_first, (size_t)t + 1));
+        const int64_t first = dswx_load<int64_t>(tile_first, (size_t)t), count = burn_count(first, dswx_load<int64_t>(tile_first, (size_t)t + 1));
         uint64_t head[DSWX_BURN_HEAD_WORDS] = {(uint64_t)count, 0, 0, 0, 0, 0, 0, 0};
         std::fill(acc.begin(), acc.end(), 0u);
         for (int64_t i = 0; i < count; ++i) {
-            const dswx_burn_vertex_t v = get_vertex(verts, (size_t)(first + i));
+            const dswx_burn_vertex_t v = dswx_load<dswx_burn_vertex_t>(verts, (size_t)(first + i));
             if ((int64_t)v.next >= count) {
                 ++head[BURN_HEAD_MALFORMED];
                 continue;
             }
-            const dswx_burn_vertex_t w = get_vertex(verts, (size_t)(first + (int64_t)v.next));
+            const dswx_burn_vertex_t w = dswx_load<dswx_burn_vertex_t>(verts, (size_t)(first + (int64_t)v.next));
             if (!burn_legal(v.x) || !burn_legal(v.y) || !burn_legal(w.x) || !burn_legal(w.y)) {
                 ++head[BURN_HEAD_MALFORMED];
                 continue;
@@ -386,7 +373,7 @@ int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, c
         }
         if (n) std::memcpy(reinterpret_cast<unsigned char*>(out->acc) + (size_t)t * (size_t)n * 4, acc.data(), (size_t)n * 4);
         if (out->head)
-            for (int w = 0; w < DSWX_BURN_HEAD_WORDS; ++w) put_u64(out->head, (size_t)(t * DSWX_BURN_HEAD_WORDS + w), head[w]);
+            for (int w = 0; w < DSWX_BURN_HEAD_WORDS; ++w) dswx_store<uint64_t>(out->head, (size_t)(t * DSWX_BURN_HEAD_WORDS + w), head[w]);
     }
     return DSWX_OK;
 }
@@ -395,9 +382,9 @@ int dswx_burn_device(dswx_ctx_t* ctx, const dswx_burn_vertex_t* verts, const int
                      int64_t height, int64_t width, const uint8_t* src, const dswx_burn_out_t* out, void* stream) {
     int64_t mask_stride, src_stride;
     if (int rc = dswx_burn_check(verts, tile_first, spec, n_tiles, height, width, src, out, &mask_stride, &src_stride, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_burn_launch(ctx, verts, tile_first, spec, n_tiles, height, width, src, mask_stride, src_stride, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) {
+        return dswx_burn_launch(ctx, verts, tile_first, spec, n_tiles, height, width, src, mask_stride, src_stride, out, s);
+    });
 }
 
 }  // extern "C"

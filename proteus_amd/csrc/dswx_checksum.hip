@@ -121,7 +121,7 @@ __global__ __launch_bounds__(CKS_BLOCK) void dswx_checksum_k(const CksArgs a) {
 int dswx_checksum_launch(dswx_ctx* ctx, const dswx_checksum_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
                          hipStream_t s) {
     if (n_planes <= 0 || n_tiles <= 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     CksArgs a = {};
@@ -196,10 +196,8 @@ int dswx_checksum_device(dswx_ctx_t* ctx, const void* plane, int32_t elem_bytes,
     if (n_tiles > 0 && (!plane || !out)) return dswx_fail(DSWX_ERR_ARG, "NULL pointer");
     if (!aligned_to(plane, (size_t)elem_bytes)) return dswx_fail(DSWX_ERR_ALIGN, "plane not aligned to its %d-byte elements", elem_bytes);
     if (!aligned_to(out, 8)) return dswx_fail(DSWX_ERR_ALIGN, "out not 8-byte aligned");
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const dswx_checksum_plane pl = {plane, (uint64_t)n_elems * (uint64_t)elem_bytes, (uint64_t)tile_stride_elems * (uint64_t)elem_bytes};
-    return dswx_checksum_launch(ctx, &pl, 1, n_tiles, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_checksum_launch(ctx, &pl, 1, n_tiles, out, s); });
 }
 
 }  // extern "C"

@@ -259,7 +259,7 @@ int dswx_compare_check_tol(double atol, double rtol) {
 int dswx_compare_launch(dswx_ctx* ctx, const dswx_compare_pair* pairs, int n_pairs, int64_t n_tiles, double atol, double rtol,
                         int equal_nan, dswx_compare_t* out, hipStream_t s) {
     if (n_pairs <= 0 || n_tiles <= 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     CmpArgs a = {};
@@ -347,10 +347,8 @@ int dswx_compare_device(dswx_ctx_t* ctx, const void* a, const void* b, int32_t k
     const size_t eb = (size_t)dswx_compare_elem_bytes(kind);
     if (!aligned_to(a, eb) || !aligned_to(b, eb)) return dswx_fail(DSWX_ERR_ALIGN, "plane not aligned to its %d-byte elements", (int)eb);
     if (!aligned_to(out, 8)) return dswx_fail(DSWX_ERR_ALIGN, "out not 8-byte aligned");
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const dswx_compare_pair pr = {a, b, kind, (uint64_t)n_elems, (uint64_t)a_stride_elems, (uint64_t)b_stride_elems};
-    return dswx_compare_launch(ctx, &pr, 1, n_tiles, atol, rtol, equal_nan, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_compare_launch(ctx, &pr, 1, n_tiles, atol, rtol, equal_nan, out, s); });
 }
 
 }  // extern "C"

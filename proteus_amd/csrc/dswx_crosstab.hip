@@ -238,7 +238,7 @@ int dswx_crosstab_check_spec(const dswx_crosstab_spec_t* spec) {
 // launch (tile counts past the 65535 of grid.y: one per 65535 tiles).
 int dswx_crosstab_launch(dswx_ctx* ctx, const dswx_crosstab_item* items, int n_pairs, int64_t n_tiles, uint64_t* out, hipStream_t s) {
     if (n_pairs <= 0 || n_tiles <= 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     if (n_pairs > DSWX_CROSSTAB_MAX_PAIRS) return dswx_fail(DSWX_ERR_ARG, "%d pairs: at most %d per launch", n_pairs, DSWX_CROSSTAB_MAX_PAIRS);
@@ -322,10 +322,8 @@ int dswx_crosstab_device(dswx_ctx_t* ctx, const void* a, const uint8_t* b, const
     const size_t eb = (size_t)dswx_histogram_elem_bytes(spec->a_kind);
     if (!aligned_to(a, eb)) return dswx_fail(DSWX_ERR_ALIGN, "plane a not aligned to its %d-byte elements", (int)eb);
     if (!aligned_to(out, 8)) return dswx_fail(DSWX_ERR_ALIGN, "out not 8-byte aligned");
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const dswx_crosstab_item it = {a, b, spec, (uint64_t)n_elems, (uint64_t)a_stride_elems, (uint64_t)b_stride_elems};
-    return dswx_crosstab_launch(ctx, &it, 1, n_tiles, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_crosstab_launch(ctx, &it, 1, n_tiles, out, s); });
 }
 
 }  // extern "C"

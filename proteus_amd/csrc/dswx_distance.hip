@@ -38,7 +38,6 @@
 // DESIGN.md section 5 has the bytes per pixel of each launch and what was measured.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
 #include <vector>
 
 #include "dswx_host.h"
@@ -373,15 +372,6 @@ __global__ void dswx_distance_key_k(unsigned long long* summary, long long n_til
     summary[t * DSWX_DISTANCE_SUMMARY_WORDS + 4] = dist_key_idx(key);
 }
 
-// unaligned host accesses (a host buffer may sit at any address)
-inline uint32_t dist_get_u32(const uint32_t* base, int64_t i) {
-    uint32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
-}
-inline void dist_put_u32(uint32_t* base, int64_t i, uint32_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 4, &v, 4); }
-inline void dist_put_u64(uint64_t* base, int64_t i, uint64_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 8, &v, 8); }
-
 }  // namespace
 
 // The checks that the device and the host entry share, in the house order: the arguments before any context, nothing
@@ -399,11 +389,7 @@ int dswx_distance_check(const uint8_t* plane, const dswx_distance_spec_t* spec, 
         return dswx_fail(DSWX_ERR_ARG, "width %lld above DSWX_DISTANCE_MAX_WIDTH (%d): a row would not fit the local memory of the row pass",
                          (long long)width, DSWX_DISTANCE_MAX_WIDTH);
     const int64_t n_elems = height * width;
-    if (*stride == 0) *stride = n_elems;
-    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
-    if (n_tiles > (1LL << 32) || *stride > (1LL << 46) || (n_tiles && (uint64_t)*stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
-    if (!plane && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
+    if (int rc = dswx_tile_geometry_check(plane, n_tiles, n_elems, stride, true)) return rc;
     if (!out->dist2) return dswx_fail(DSWX_ERR_ARG, "dist2 is NULL: it is the working array and always required");
     if (out->within && spec->max_radius == 0)
         return dswx_fail(DSWX_ERR_ARG, "within is wanted but max_radius is 0: the ring needs a radius");
@@ -419,7 +405,7 @@ int dswx_distance_check(const uint8_t* plane, const dswx_distance_spec_t* spec, 
 int dswx_distance_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height,
                          int64_t width, int64_t stride, const dswx_distance_out_t* out, hipStream_t s) {
     if (n_tiles == 0 || height == 0 || width == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     DistArgs a = {};
@@ -479,12 +465,12 @@ int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, i
             int64_t last = -1;
             for (int64_t y = 0; y < height; ++y) {
                 if (label_is_member(bits, tile[y * width + x])) last = y;
-                dist_put_u32(d, y * width + x, last < 0 ? DIST_FAR : (uint32_t)(y - last));
+                dswx_store<uint32_t>(d, y * width + x, last < 0 ? DIST_FAR : (uint32_t)(y - last));
             }
             int64_t next = -1;
             for (int64_t y = height - 1; y >= 0; --y) {
                 if (label_is_member(bits, tile[y * width + x])) next = y;
-                dist_put_u32(d, y * width + x, dist_entry(dist_get_u32(d, y * width + x), next < 0 ? DIST_FAR : (uint32_t)(next - y), R));
+                dswx_store<uint32_t>(d, y * width + x, dist_entry(dswx_load<uint32_t>(d, y * width + x), next < 0 ? DIST_FAR : (uint32_t)(next - y), R));
             }
         }
         // the row pass: from every pixel outward until the step alone cannot win.  TERMINATES: k rises to the width.
@@ -493,7 +479,7 @@ int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, i
         for (int64_t y = 0; y < height; ++y) {
             bool any = false;
             for (int64_t x = 0; x < width; ++x) {
-                row[(size_t)x] = dist_entry_dy(dist_get_u32(d, y * width + x));
+                row[(size_t)x] = dist_entry_dy(dswx_load<uint32_t>(d, y * width + x));
                 any = any || row[(size_t)x] != DIST_NO_DY;
             }
             for (int64_t x = 0; x < width; ++x) {
@@ -512,8 +498,8 @@ int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, i
                 const int64_t p = y * width + x;
                 const bool reached = best != limit;
                 const uint32_t d2 = reached ? best : DSWX_DISTANCE_NONE;
-                dist_put_u32(d, p, d2);
-                if (near) dist_put_u32(near, p, reached ? (uint32_t)((y + row[best_x]) * width + best_x) : DSWX_DISTANCE_NONE);
+                dswx_store<uint32_t>(d, p, d2);
+                if (near) dswx_store<uint32_t>(near, p, reached ? (uint32_t)((y + row[best_x]) * width + best_x) : DSWX_DISTANCE_NONE);
                 if (out->within) out->within[(size_t)t * (size_t)n + (size_t)p] = (uint8_t)dist_within(tile[p], d2, (unsigned)spec->mark);
                 if (!reached) {
                     ++sum[2];
@@ -529,7 +515,7 @@ int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, i
         sum[3] = dist_key_d2(key);
         sum[4] = dist_key_idx(key);
         if (out->summary)
-            for (int w = 0; w < DSWX_DISTANCE_SUMMARY_WORDS; ++w) dist_put_u64(out->summary, t * DSWX_DISTANCE_SUMMARY_WORDS + w, sum[w]);
+            for (int w = 0; w < DSWX_DISTANCE_SUMMARY_WORDS; ++w) dswx_store<uint64_t>(out->summary, t * DSWX_DISTANCE_SUMMARY_WORDS + w, sum[w]);
     }
     return DSWX_OK;
 }
@@ -537,9 +523,7 @@ int dswx_distance_host(const uint8_t* plane, const dswx_distance_spec_t* spec, i
 int dswx_distance_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_distance_spec_t* spec, int64_t n_tiles, int64_t height,
                          int64_t width, int64_t stride, const dswx_distance_out_t* out, void* stream) {
     if (int rc = dswx_distance_check(plane, spec, n_tiles, height, width, &stride, out, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_distance_launch(ctx, plane, spec, n_tiles, height, width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_distance_launch(ctx, plane, spec, n_tiles, height, width, stride, out, s); });
 }
 
 }  // extern "C"

@@ -312,9 +312,6 @@ __global__ __launch_bounds__(GRID_BLOCK) void dswx_grid_k(const GridArgs a) {
     }
 }
 
-// unaligned host stores (a host buffer may sit at any address)
-inline void put_u32(uint32_t* base, int64_t i, uint32_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 4, &v, 4); }
-
 }  // namespace
 
 // The checks that the device and the host entry share, in the house order: the arguments before any context, nothing
@@ -329,22 +326,14 @@ int dswx_grid_check(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t 
     if (n_tiles < 0 || height < 0 || width < 0 || *stride < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
     if (height > GRID_MAX_SIDE || width > GRID_MAX_SIDE) return dswx_fail(DSWX_ERR_ARG, "raster too large");
     const int64_t n_elems = height * width;
-    if (*stride == 0) *stride = n_elems;
-    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
-    if (n_tiles > (1LL << 32) || *stride > (1LL << 46) || (n_tiles && (uint64_t)*stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
+    if (int rc = dswx_tile_stride_check(stride, n_elems)) return rc;
+    if (int rc = dswx_tile_extent_check(*stride, n_tiles, true)) return rc;
     const int64_t ch = spec->cell_h < height ? spec->cell_h : height, cw = spec->cell_w < width ? spec->cell_w : width;
     if (ch * cw > DSWX_GRID_MAX_CELL_PIXELS)
         return dswx_fail(DSWX_ERR_ARG, "a cell of %lld x %lld pixels is above DSWX_GRID_MAX_CELL_PIXELS (%d)", (long long)ch,
                          (long long)cw, DSWX_GRID_MAX_CELL_PIXELS);
-    if (!plane && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
-    bool any = out->share || out->coverage || out->major;
-    for (int k = 0; k < DSWX_GRID_MAX_CATS; ++k) {
-        if (out->count[k] && k >= spec->n_cats)
-            return dswx_fail(DSWX_ERR_ARG, "count[%d] is not NULL but n_cats is %d", k, spec->n_cats);
-        any = any || out->count[k];
-    }
-    if (!any) return dswx_fail(DSWX_ERR_ARG, "every output is NULL");
+    if (int rc = dswx_tile_plane_check(plane, n_tiles, n_elems)) return rc;
+    if (int rc = dswx_outputs_check(out->count, DSWX_GRID_MAX_CATS, spec->n_cats, out->share || out->coverage || out->major)) return rc;
     if (align)
         for (int k = 0; k < DSWX_GRID_MAX_CATS; ++k)
             if (!aligned_to(out->count[k], 4)) return dswx_fail(DSWX_ERR_ALIGN, "count[%d] not 4-byte aligned", k);
@@ -355,7 +344,7 @@ int dswx_grid_check(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t 
 int dswx_grid_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, int64_t stride, const dswx_grid_out_t* out, hipStream_t s) {
     if (n_tiles == 0 || height == 0 || width == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     const GridGeometry g = grid_geometry(height, width, spec->cell_h, spec->cell_w);
@@ -427,7 +416,7 @@ int dswx_grid_host(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n
                 }
                 const int64_t o = (t * gh + gy) * gw + gx;
                 for (int k = 0; k < DSWX_GRID_MAX_CATS; ++k)
-                    if (out->count[k]) put_u32(out->count[k], o, count[k]);
+                    if (out->count[k]) dswx_store<uint32_t>(out->count[k], (size_t)o, count[k]);
                 if (out->share) out->share[o] = (uint8_t)grid_share(count);
                 if (out->coverage) out->coverage[o] = (uint8_t)grid_coverage(count, (uint32_t)((rb - ra) * (cb - ca)));
                 if (out->major) out->major[o] = (uint8_t)grid_major(count);
@@ -440,9 +429,7 @@ int dswx_grid_host(const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n
 int dswx_grid_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_grid_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, int64_t stride, const dswx_grid_out_t* out, void* stream) {
     if (int rc = dswx_grid_check(plane, spec, n_tiles, height, width, &stride, out, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_grid_launch(ctx, plane, spec, n_tiles, height, width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_grid_launch(ctx, plane, spec, n_tiles, height, width, stride, out, s); });
 }
 
 }  // extern "C"

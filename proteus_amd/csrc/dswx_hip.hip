@@ -724,7 +724,7 @@ static int classify_device_impl(dswx_ctx_t* ctx, const dswx_params_t* params, in
     hipStream_t s = pl.s = dswx_stream_of(ctx, stream);
     if (n_tiles == 0 || n_pixels == 0) {
         if (counters && n_tiles > 0) HIP_TRY(hipMemsetAsync(counters, 0, (size_t)n_tiles * 3 * sizeof(int64_t), s));
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     if (int wrc = dswx_ws_enter(ctx, s)) return wrc;

@@ -186,7 +186,7 @@ int dswx_histogram_check_kind(int kind, int shift) {
 int dswx_histogram_launch(dswx_ctx* ctx, const dswx_histogram_plane* planes, int n_planes, int64_t n_tiles, uint64_t* out,
                           hipStream_t s) {
     if (n_planes <= 0 || n_tiles <= 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     HistArgs a = {};
@@ -261,10 +261,8 @@ int dswx_histogram_device(dswx_ctx_t* ctx, const void* plane, int32_t kind, int3
     const size_t eb = (size_t)dswx_histogram_elem_bytes(kind);
     if (!aligned_to(plane, eb)) return dswx_fail(DSWX_ERR_ALIGN, "plane not aligned to its %d-byte elements", (int)eb);
     if (!aligned_to(out, 8)) return dswx_fail(DSWX_ERR_ALIGN, "out not 8-byte aligned");
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
     const dswx_histogram_plane pl = {plane, kind, lo, shift, (uint64_t)n_elems, (uint64_t)tile_stride_elems};
-    return dswx_histogram_launch(ctx, &pl, 1, n_tiles, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_histogram_launch(ctx, &pl, 1, n_tiles, out, s); });
 }
 
 }  // extern "C"

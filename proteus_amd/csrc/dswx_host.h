@@ -142,6 +142,62 @@ struct dswx_call_scratch {
 
 static inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// Unaligned host accesses (a host buffer may sit at any address): element `index` of an array of T that begins at `base`.
+// The index is ALWAYS in elements of T; a field at a byte offset is addressed at the call, static_cast<unsigned char*>(base) + bytes.
+template <class T> static inline T dswx_load(const void* base, size_t index) {
+    T v;
+    std::memcpy(&v, static_cast<const unsigned char*>(base) + index * sizeof(T), sizeof(T));
+    return v;
+}
+template <class T> static inline void dswx_store(void* base, size_t index, T v) {
+    std::memcpy(static_cast<unsigned char*>(base) + index * sizeof(T), &v, sizeof(T));
+}
+
+// ---- The frame of a raster entry.  The geometry refusals of a tiled plane, in the house order; an entry with a refusal of
+// its own between two of them calls the three parts, every other one dswx_tile_geometry_check.
+// A stride of 0 is the tile itself; `what` names the stride in the refusal.
+static inline int dswx_tile_stride_check(int64_t* stride, int64_t n_elems, const char* what = "tile_stride") {
+    if (*stride == 0) *stride = n_elems;
+    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "%s smaller than the tile", what);
+    return DSWX_OK;
+}
+// `tiles32`: the kernels number the tiles in 32 bits (the stack and the mosaic have a smaller limit of their own)
+static inline int dswx_tile_extent_check(int64_t stride, int64_t n_tiles, bool tiles32) {
+    if ((tiles32 && n_tiles > (1LL << 32)) || stride > (1LL << 46) || (n_tiles && (uint64_t)stride > (1ull << 46) / (uint64_t)n_tiles))
+        return dswx_fail(DSWX_ERR_ARG, "plane too large");
+    return DSWX_OK;
+}
+static inline int dswx_tile_plane_check(const void* plane, int64_t n_tiles, int64_t n_elems, const char* what = "plane") {
+    if (!plane && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "%s is NULL", what);
+    return DSWX_OK;
+}
+static inline int dswx_tile_geometry_check(const void* plane, int64_t n_tiles, int64_t n_elems, int64_t* stride, bool tiles32) {
+    if (int rc = dswx_tile_stride_check(stride, n_elems)) return rc;
+    if (int rc = dswx_tile_extent_check(*stride, n_tiles, tiles32)) return rc;
+    return dswx_tile_plane_check(plane, n_tiles, n_elems);
+}
+
+// Per-category count outputs (`count[max_cats]`, of any element type): none beyond n_cats, and some output wanted at all
+template <class P> static inline int dswx_outputs_check(P* const* count, int max_cats, int n_cats, bool any_other) {
+    bool any = any_other;
+    for (int k = 0; k < max_cats; ++k) {
+        if (count[k] && k >= n_cats) return dswx_fail(DSWX_ERR_ARG, "count[%d] is not NULL but n_cats is %d", k, n_cats);
+        any = any || count[k];
+    }
+    if (!any) return dswx_fail(DSWX_ERR_ARG, "every output is NULL");
+    return DSWX_OK;
+}
+
+// The tail of a *_device entry, behind the checks of its arguments: the context, its device, and `launch` on the caller's
+// stream or the context's own.
+template <class Launch> static inline int dswx_device_entry(dswx_ctx* ctx, void* stream, Launch launch) {
+    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    return launch(dswx_stream_of(ctx, stream));
+}
+// last_kernel of a launch that had nothing to do
+constexpr const char* DSWX_NO_KERNEL = "none (empty input)";
+
 // Grows workspace `w` of a context to at least `need` bytes (dswx_hip.hip): the one place a workspace is freed and
 // allocated again.  The free waits first for the work that may still use the old allocation: stream `s` (after
 // dswx_ws_enter that covers the context's work on other streams too), or the whole device.

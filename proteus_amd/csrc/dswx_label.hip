@@ -446,23 +446,14 @@ __global__ void dswx_label_key_k(unsigned long long* summary, long long n_tiles)
     summary[t * DSWX_LABEL_SUMMARY_WORDS + 3] = label_key_label(key);
 }
 
-// unaligned host accesses (a host buffer may sit at any address)
-inline uint32_t get_u32(const uint32_t* base, int64_t i) {
-    uint32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
-}
-inline void put_u32(uint32_t* base, int64_t i, uint32_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 4, &v, 4); }
-inline void put_u64(uint64_t* base, int64_t i, uint64_t v) { std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 8, &v, 8); }
-
 // The scalar union-find of the host entry, on the caller's label plane in the encoding of the kernels (0 / 1 + parent).
 // TERMINATES: the parent of p is at most p, so p strictly decreases; the walk halves the path behind it.
 inline uint32_t host_find(uint32_t* lab, uint32_t p) {
     for (;;) {
-        const uint32_t q = get_u32(lab, p) - 1u;
+        const uint32_t q = dswx_load<uint32_t>(lab, p) - 1u;
         if (q == p) return p;
-        const uint32_t g = get_u32(lab, q);              // (the grandparent, <= q + 1: still at or below p)
-        put_u32(lab, p, g);
+        const uint32_t g = dswx_load<uint32_t>(lab, q);              // (the grandparent, <= q + 1: still at or below p)
+        dswx_store<uint32_t>(lab, p, g);
         p = q;
     }
 }
@@ -470,8 +461,8 @@ inline void host_union(uint32_t* lab, uint32_t a, uint32_t b) {
     a = host_find(lab, a);
     b = host_find(lab, b);
     if (a == b) return;
-    if (a < b) put_u32(lab, b, a + 1u);
-    else put_u32(lab, a, b + 1u);
+    if (a < b) dswx_store<uint32_t>(lab, b, a + 1u);
+    else dswx_store<uint32_t>(lab, a, b + 1u);
 }
 
 }  // namespace
@@ -490,11 +481,7 @@ int dswx_label_check(const uint8_t* plane, const dswx_label_spec_t* spec, int64_
     if (height > LABEL_MAX_PIXELS || width > LABEL_MAX_PIXELS || height * width > LABEL_MAX_PIXELS)
         return dswx_fail(DSWX_ERR_ARG, "raster too large: height * width above 2^31, a label would not fit 32 bits");
     const int64_t n_elems = height * width;
-    if (*stride == 0) *stride = n_elems;
-    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
-    if (n_tiles > (1LL << 32) || *stride > (1LL << 46) || (n_tiles && (uint64_t)*stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
-    if (!plane && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
+    if (int rc = dswx_tile_geometry_check(plane, n_tiles, n_elems, stride, true)) return rc;
     if (!out->label) return dswx_fail(DSWX_ERR_ARG, "label is NULL: it is the working array and always required");
     if (!out->size && (out->sieved || out->summary))
         return dswx_fail(DSWX_ERR_ARG, "size is NULL but %s is wanted: size is required for it", out->sieved ? "sieved" : "summary");
@@ -510,7 +497,7 @@ int dswx_label_check(const uint8_t* plane, const dswx_label_spec_t* spec, int64_
 int dswx_label_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height,
                       int64_t width, int64_t stride, const dswx_label_out_t* out, hipStream_t s) {
     if (n_tiles == 0 || height == 0 || width == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     LabelArgs a = {};
@@ -572,34 +559,34 @@ int dswx_label_host(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t
             for (int64_t x = 0; x < width; ++x) {
                 const int64_t p = y * width + x;
                 if (!label_is_member(bits, tile[p])) {
-                    put_u32(lab, p, 0u);
+                    dswx_store<uint32_t>(lab, p, 0u);
                     continue;
                 }
-                put_u32(lab, p, (uint32_t)p + 1u);
-                if (x > 0 && get_u32(lab, p - 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - 1));
+                dswx_store<uint32_t>(lab, p, (uint32_t)p + 1u);
+                if (x > 0 && dswx_load<uint32_t>(lab, p - 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - 1));
                 if (y > 0) {
-                    if (get_u32(lab, p - width)) host_union(lab, (uint32_t)p, (uint32_t)(p - width));
-                    if (conn8 && x > 0 && get_u32(lab, p - width - 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - width - 1));
-                    if (conn8 && x + 1 < width && get_u32(lab, p - width + 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - width + 1));
+                    if (dswx_load<uint32_t>(lab, p - width)) host_union(lab, (uint32_t)p, (uint32_t)(p - width));
+                    if (conn8 && x > 0 && dswx_load<uint32_t>(lab, p - width - 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - width - 1));
+                    if (conn8 && x + 1 < width && dswx_load<uint32_t>(lab, p - width + 1)) host_union(lab, (uint32_t)p, (uint32_t)(p - width + 1));
                 }
             }
         // in rising order the parent of a pixel is flat already when the pixel is reached
         uint32_t* size = out->size ? reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(out->size) + (size_t)t * (size_t)n * 4) : nullptr;
         for (int64_t p = 0; p < n; ++p) {
-            const uint32_t v = get_u32(lab, p);
-            if (size) put_u32(size, p, 0u);
+            const uint32_t v = dswx_load<uint32_t>(lab, p);
+            if (size) dswx_store<uint32_t>(size, p, 0u);
             if (!v) continue;
-            const uint32_t r = get_u32(lab, v - 1u);
-            put_u32(lab, p, r);
-            if (size) put_u32(size, r - 1u, get_u32(size, r - 1u) + 1u);
+            const uint32_t r = dswx_load<uint32_t>(lab, v - 1u);
+            dswx_store<uint32_t>(lab, p, r);
+            if (size) dswx_store<uint32_t>(size, r - 1u, dswx_load<uint32_t>(size, r - 1u) + 1u);
         }
         if (!size) continue;
         uint64_t sum[DSWX_LABEL_SUMMARY_WORDS] = {};
         uint64_t key = 0;
         for (int64_t p = 0; p < n; ++p) {
-            const uint32_t v = get_u32(lab, p);
-            const uint32_t sz = v ? get_u32(size, v - 1u) : 0u;                  // (a root is before its pixels: still its count)
-            if (v && (int64_t)v != p + 1) put_u32(size, p, sz);
+            const uint32_t v = dswx_load<uint32_t>(lab, p);
+            const uint32_t sz = v ? dswx_load<uint32_t>(size, v - 1u) : 0u;                  // (a root is before its pixels: still its count)
+            if (v && (int64_t)v != p + 1) dswx_store<uint32_t>(size, p, sz);
             if (out->sieved) out->sieved[(size_t)t * (size_t)n + (size_t)p] = (uint8_t)label_sieve(tile[p], v != 0u, sz, spec->min_size, (unsigned)spec->replace);
             if (!v) continue;
             ++sum[1];
@@ -616,7 +603,7 @@ int dswx_label_host(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t
         sum[2] = label_key_size(key);
         sum[3] = label_key_label(key);
         if (out->summary)
-            for (int w = 0; w < DSWX_LABEL_SUMMARY_WORDS; ++w) put_u64(out->summary, t * DSWX_LABEL_SUMMARY_WORDS + w, sum[w]);
+            for (int w = 0; w < DSWX_LABEL_SUMMARY_WORDS; ++w) dswx_store<uint64_t>(out->summary, t * DSWX_LABEL_SUMMARY_WORDS + w, sum[w]);
     }
     return DSWX_OK;
 }
@@ -624,9 +611,7 @@ int dswx_label_host(const uint8_t* plane, const dswx_label_spec_t* spec, int64_t
 int dswx_label_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_label_spec_t* spec, int64_t n_tiles, int64_t height,
                       int64_t width, int64_t stride, const dswx_label_out_t* out, void* stream) {
     if (int rc = dswx_label_check(plane, spec, n_tiles, height, width, &stride, out, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_label_launch(ctx, plane, spec, n_tiles, height, width, stride, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_label_launch(ctx, plane, spec, n_tiles, height, width, stride, out, s); });
 }
 
 }  // extern "C"

@@ -5,7 +5,6 @@
 #pragma once
 
 #include <cstdint>
-#include <cstring>
 
 #define MESH_HD __host__ __device__ __forceinline__
 
@@ -28,7 +27,7 @@ MESH_HD int64_t mesh_coord(int64_t v00, int64_t v01, int64_t v10, int64_t v11, i
     return mesh_round(mesh_numerator(v00, v01, v10, v11, fx, fy, s), s);
 }
 
-// The position (sx, sy); node(k) returns int32 number k of the mesh of this tile (a device load, mesh_node_at on the host).
+// The position (sx, sy); node(k) returns int32 number k of the mesh of this tile (a device load, dswx_load of dswx_host.h on the host).
 template <class Node> MESH_HD void mesh_position(Node node, int s, int64_t mesh_w, int64_t X, int64_t Y, int64_t* sx, int64_t* sy) {
     const int64_t step = (int64_t)1 << s;
     const int64_t i = Y >> s, fy = Y & (step - 1), j = X >> s, fx = X & (step - 1);
@@ -43,13 +42,6 @@ template <class Node> MESH_HD void mesh_position(Node node, int s, int64_t mesh_
 MESH_HD void mesh_cell_linear(int v00, int v01, int v10, int v11, int gy, int hy, int s, long long& a, long long& b) {
     a = ((long long)gy * v00 + (long long)hy * v10) * (1LL << s);
     b = (long long)gy * v01 - (long long)gy * v00 + (long long)hy * v11 - (long long)hy * v10;
-}
-
-// int32 number k of a host mesh, which may sit at any address
-inline int64_t mesh_node_at(const int32_t* base, int64_t k) {
-    int32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)k * 4, 4);
-    return v;
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // dswx_mosaic.hip -- the tiles of a plane placed on one canvas and composited per canvas pixel (DSWX_HAS_MOSAIC, additive to
 // ABI v7): a stack with placements.  include/dswx_hip.h "mosaic" states the definition; proteus_amd/mosaic.py is its numpy
 // statement and dswx_mosaic_host below the scalar one.  The per-byte and per-pixel rule is dswx_stack_rule.h, unchanged and
-// compiled for both sides; what is new here is geometry: which tiles cover a pixel.
+// compiled for both sides, and the table, the unit, the stores and the checks of the outputs are dswx_stack_core.h, shared with
+// the stack entries; what is here is geometry: which tiles cover a pixel.
 //
 // OWNERSHIP.  A workgroup of 256 threads owns a rectangle of the canvas, MOSAIC_ROWS = 4 rows x MOSAIC_COLS = 1024 columns,
 // blocks numbered row-major along grid.x.  One wave owns each row, so "does tile t cover my row" is the same in every lane:
@@ -23,7 +24,7 @@
 //
 // THE WALK.  The list is consumed in rounds of MOSAIC_U = 8 entries: the 16-byte loads of the round are issued before the
 // first is counted, as in the stack kernel, 128 bytes in flight per thread; the table of increments is the stack kernel's
-// eight lane-indexed replicas (dswx_stack.hip has the bank arithmetic).  For a list entry the unit of a lane is one of three
+// eight lane-indexed replicas (dswx_stack_core.h has the bank arithmetic).  For a list entry the unit of a lane is one of three
 // cases.  Wholly inside the tile's columns: one unaligned 16-byte load and exactly the stack kernel's unit (gfx950 performs
 // unaligned 16-byte global accesses in hardware).  Wholly outside, or the row not covered (the same in every lane): skipped.
 // Cut by a tile edge: ALSO one 16-byte load, from the unit's first pixel on -- those 16 bytes leave the tile's row but they
@@ -47,26 +48,18 @@
 // row, cut inside the canvas), two v_lshl_add_u64 for the address.  Measured: tools/mosaic_rate.py, DESIGN.md section 5.
 #include <hip/hip_runtime.h>
 #include <cstdio>
-#include <cstring>
 
-#include "dswx_host.h"
-#include "dswx_stack_rule.h"
+#include "dswx_stack_core.h"
 
 namespace {
 
-typedef u32x4 __attribute__((aligned(1))) u32x4_b;      // 16 bytes anywhere
-
-constexpr int MOSAIC_BLOCK = 256;                        // threads: one table entry, one tile of a chunk each
-constexpr int MOSAIC_PPT = 16;                           // pixels per thread = bytes per load
-constexpr int MOSAIC_U = 8;                              // loads (list entries) in flight per thread
-constexpr int MOSAIC_REPLICAS = 8;                       // of the increment table: lane l reads replica l & 7
+// the stack kernel's constants under the names that the text above and last_kernel use
+constexpr int MOSAIC_BLOCK = STACK_BLOCK, MOSAIC_PPT = STACK_PPT, MOSAIC_U = STACK_U, MOSAIC_REPLICAS = STACK_REPLICAS;
 constexpr int MOSAIC_ROWS = MOSAIC_BLOCK / 64;           // canvas rows of a block: one wave each
 constexpr int MOSAIC_COLS = 64 * MOSAIC_PPT;             // canvas columns of a block
 constexpr int MOSAIC_CHUNK = MOSAIC_BLOCK;               // placements tested per step
 constexpr int MOSAIC_LIST = 2 * MOSAIC_CHUNK;            // surviving tiles held in LDS
 constexpr int64_t MOSAIC_MAX_SIDE = 1LL << 30;
-static_assert(MOSAIC_BLOCK == 256, "the table has one entry per thread of a block");
-static_assert(DSWX_STACK_MAX_CATS * 16 == 64 && DSWX_STACK_MAX_TILES < (1 << 16), "four uint16 fields that cannot carry");
 
 struct MosaicArgs {
     const unsigned char* plane;
@@ -75,31 +68,11 @@ struct MosaicArgs {
     const int* place;                                    // [n_tiles][2] = row0, col0
     int n_tiles, height, width, canvas_h, canvas_w;
     unsigned nbx;                                        // blocks along a canvas row
-    int n_cats, fill, outside;
+    StackCoreArgs c;                                     // outputs and spec
+    int outside;
     int neutral;                                         // a byte that is not an observation, -1 if every byte is one
-    unsigned short* count[DSWX_STACK_MAX_CATS];
-    unsigned char* last;
-    unsigned short* last_index;
-    unsigned char* share;
-    unsigned char cat_of_byte[256];
 };
 static_assert(sizeof(MosaicArgs) <= 4096, "kernel arguments");
-
-// one 16-byte unit of tile t into the 16 pixels of a thread, as stack_unit of dswx_stack.hip; MASKED: only the pixels whose bit
-// of `m` is set are covered, the increment of the others is made zero -- which by the rule is "not an observation"
-template <bool LATEST, bool MASKED>
-__device__ __forceinline__ void mosaic_unit(const u32x4& v, unsigned m, uint32_t t, const uint64_t* mine, uint64_t (&acc)[MOSAIC_PPT],
-                                            uint32_t (&latest)[MOSAIC_PPT]) {
-    uint64_t inc[MOSAIC_PPT];
-#pragma unroll
-    for (int i = 0; i < MOSAIC_PPT; ++i) inc[i] = mine[((v[i / 4] >> (8 * (i % 4))) & 0xffu) * MOSAIC_REPLICAS];
-#pragma unroll
-    for (int i = 0; i < MOSAIC_PPT; ++i) {
-        if (MASKED) inc[i] = ((m >> i) & 1u) ? inc[i] : 0ull;
-        if (LATEST) stack_step(acc[i], latest[i], inc[i], t, (v[i / 4] >> (8 * (i % 4))) & 0xffu);
-        else acc[i] += inc[i];
-    }
-}
 
 // The bytes of `w` whose bit of `mask` is not set replaced by the byte `neutral`: what a cut unit does to the pixels that the
 // tile does not cover, where the spec has a byte that is not an observation -- the unit then counts as a whole one.
@@ -133,36 +106,6 @@ __device__ __forceinline__ u32x4 shift_bytes(const u32x4& w, int d) {
     return u32x4{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
 }
 
-// 16 values, or the first n of them, to consecutive elements at any element-aligned address
-template <typename F> __device__ __forceinline__ void store_u16(unsigned short* dst, int n, F value) {
-    if (n == MOSAIC_PPT) {
-        u32x4 lo, hi;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            lo[j] = value(2 * j) | (value(2 * j + 1) << 16);
-            hi[j] = value(8 + 2 * j) | (value(8 + 2 * j + 1) << 16);
-        }
-        stg_u<u32x4_u, u32x4, false>(dst, lo);
-        stg_u<u32x4_u, u32x4, false>(dst + 8, hi);
-    } else {
-#pragma unroll
-        for (int i = 0; i < MOSAIC_PPT; ++i)
-            if (i < n) dst[i] = (unsigned short)value(i);
-    }
-}
-template <typename F> __device__ __forceinline__ void store_u8(unsigned char* dst, int n, F value) {
-    if (n == MOSAIC_PPT) {
-        u32x4 w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = value(4 * j) | (value(4 * j + 1) << 8) | (value(4 * j + 2) << 16) | (value(4 * j + 3) << 24);
-        stg_u<u32x4_b, u32x4, false>(dst, w);
-    } else {
-#pragma unroll
-        for (int i = 0; i < MOSAIC_PPT; ++i)
-            if (i < n) dst[i] = (unsigned char)value(i);
-    }
-}
-
 // What the walk needs of a surviving tile, worked out ONCE per tile and block by the thread that culled it, so that the walk
 // is 32-bit arithmetic: the tile row of the block's first row and the tile column of its first column -- both fit an int
 // BECAUSE the tile meets the rectangle: -MOSAIC_ROWS < rr < height, -MOSAIC_COLS < cc < width -- and the byte offset of that
@@ -178,15 +121,9 @@ __global__ __launch_bounds__(MOSAIC_BLOCK, 3) void dswx_mosaic_k(const MosaicArg
     __shared__ __attribute__((aligned(16))) MosaicEntry list_e[MOSAIC_LIST];
     __shared__ __attribute__((aligned(8))) long long list_base[MOSAIC_LIST];
     __shared__ int wave_hits[MOSAIC_ROWS];
-    {
-        const uint64_t inc = stack_increment(a.cat_of_byte, a.n_cats, threadIdx.x);
-#pragma unroll
-        for (int r = 0; r < MOSAIC_REPLICAS; ++r) tab[threadIdx.x * MOSAIC_REPLICAS + r] = inc;
-    }
-    __syncthreads();
+    const uint64_t* const mine = stack_fill_table(tab, a.c);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint64_t* const mine = tab + (lane & (MOSAIC_REPLICAS - 1));
     // the rectangle of the block, [Y0, Y1) x [X0, X1), and the unit of this thread: row Y, columns X .. X + nvalid - 1
     const unsigned by = blockIdx.x / a.nbx, bx = blockIdx.x - by * a.nbx;
     const long long Y0 = (long long)by * MOSAIC_ROWS, X0 = (long long)bx * MOSAIC_COLS;
@@ -198,7 +135,7 @@ __global__ __launch_bounds__(MOSAIC_BLOCK, 3) void dswx_mosaic_k(const MosaicArg
     const int lane16 = lane * MOSAIC_PPT;
     const unsigned real = (1u << nvalid) - 1u;                       // the pixels of the unit that are pixels of the canvas
     const long long wave_rows = (long long)wave * a.width;           // bytes from the block's first row to this wave's
-    const uint32_t none = stack_latest_none(a.fill);
+    const uint32_t none = stack_latest_none(a.c.fill);
     uint64_t acc[MOSAIC_PPT];
     uint32_t latest[MOSAIC_PPT];
 #pragma unroll
@@ -296,8 +233,8 @@ __global__ __launch_bounds__(MOSAIC_BLOCK, 3) void dswx_mosaic_k(const MosaicArg
                     }
 #pragma unroll
                     for (int j = 0; j < MOSAIC_U; ++j) {
-                        if (m[j] == 0xffffu) mosaic_unit<LATEST, false>(v[j], m[j], tile[j], mine, acc, latest);
-                        else if (m[j]) mosaic_unit<LATEST, true>(v[j], m[j], tile[j], mine, acc, latest);
+                        if (m[j] == 0xffffu) stack_unit<LATEST, false>(v[j], m[j], tile[j], mine, acc, latest);
+                        else if (m[j]) stack_unit<LATEST, true>(v[j], m[j], tile[j], mine, acc, latest);
                     }
                 }
             }
@@ -333,21 +270,10 @@ __global__ __launch_bounds__(MOSAIC_BLOCK, 3) void dswx_mosaic_k(const MosaicArg
     const unsigned outside = (unsigned)a.outside;
 #pragma unroll
     for (int k = 0; k < DSWX_STACK_MAX_CATS; ++k)
-        if (a.count[k]) store_u16(a.count[k] + e, nvalid, [&](int i) { return stack_count(acc[i], k); });
-    if (LATEST && a.last) store_u8(a.last + e, nvalid, [&](int i) { return ((covered >> i) & 1u) ? stack_last(latest[i]) : outside; });
-    if (LATEST && a.last_index) store_u16(a.last_index + e, nvalid, [&](int i) { return stack_last_index(latest[i]); });
-    if (a.share) store_u8(a.share + e, nvalid, [&](int i) { return stack_share(acc[i]); });
-}
-
-// unaligned host accesses (a host buffer may sit at any address)
-inline void put_u16(uint16_t* base, int64_t i, unsigned v) {
-    const uint16_t h = (uint16_t)v;
-    std::memcpy(reinterpret_cast<unsigned char*>(base) + (size_t)i * 2, &h, 2);
-}
-inline int64_t get_i32(const int32_t* base, int64_t i) {
-    int32_t v;
-    std::memcpy(&v, reinterpret_cast<const unsigned char*>(base) + (size_t)i * 4, 4);
-    return v;
+        if (a.c.count[k]) store_u16(a.c.count[k] + e, nvalid, [&](int i) { return stack_count(acc[i], k); });
+    if (LATEST && a.c.last) store_u8(a.c.last + e, nvalid, [&](int i) { return ((covered >> i) & 1u) ? stack_last(latest[i]) : outside; });
+    if (LATEST && a.c.last_index) store_u16(a.c.last_index + e, nvalid, [&](int i) { return stack_last_index(latest[i]); });
+    if (a.c.share) store_u8(a.c.share + e, nvalid, [&](int i) { return stack_share(acc[i]); });
 }
 
 }  // namespace
@@ -359,9 +285,7 @@ int dswx_mosaic_check(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int6
                       bool align) {
     if (!spec) return dswx_fail(DSWX_ERR_ARG, "spec is NULL");
     if (!out) return dswx_fail(DSWX_ERR_ARG, "out is NULL");
-    if (spec->n_cats < 1 || spec->n_cats > DSWX_STACK_MAX_CATS)
-        return dswx_fail(DSWX_ERR_ARG, "n_cats %d outside 1 .. %d", spec->n_cats, DSWX_STACK_MAX_CATS);
-    if (spec->fill < 0 || spec->fill > 255) return dswx_fail(DSWX_ERR_ARG, "fill %d outside 0 .. 255", spec->fill);
+    if (int rc = stack_spec_check(spec->n_cats, spec->fill)) return rc;
     if (spec->outside < 0 || spec->outside > 255) return dswx_fail(DSWX_ERR_ARG, "outside %d outside 0 .. 255", spec->outside);
     if (spec->reserved != 0) return dswx_fail(DSWX_ERR_ARG, "reserved is %d, not 0", spec->reserved);
     if (n_tiles < 0 || height < 0 || width < 0 || *stride < 0) return dswx_fail(DSWX_ERR_ARG, "negative size");
@@ -370,28 +294,13 @@ int dswx_mosaic_check(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int6
     if (canvas_h > MOSAIC_MAX_SIDE || canvas_w > MOSAIC_MAX_SIDE || (canvas_w && canvas_h > (1LL << 46) / canvas_w))
         return dswx_fail(DSWX_ERR_ARG, "canvas %lld x %lld too large", (long long)canvas_h, (long long)canvas_w);
     const int64_t n_elems = height * width;
-    if (*stride == 0) *stride = n_elems;
-    if (*stride < n_elems) return dswx_fail(DSWX_ERR_ARG, "tile_stride smaller than the tile");
-    if (n_tiles > DSWX_STACK_MAX_TILES)
-        return dswx_fail(DSWX_ERR_ARG, "n_tiles %lld above DSWX_STACK_MAX_TILES (%d): a count would not fit its uint16",
-                         (long long)n_tiles, DSWX_STACK_MAX_TILES);
-    if (*stride > (1LL << 46) || (n_tiles && (uint64_t)*stride > (1ull << 46) / (uint64_t)n_tiles))
-        return dswx_fail(DSWX_ERR_ARG, "plane too large");
-    if (!plane && n_tiles > 0 && n_elems > 0) return dswx_fail(DSWX_ERR_ARG, "plane is NULL");
+    if (int rc = dswx_tile_stride_check(stride, n_elems)) return rc;
+    if (int rc = stack_tiles_check(n_tiles)) return rc;
+    if (int rc = dswx_tile_extent_check(*stride, n_tiles, false)) return rc;
+    if (int rc = dswx_tile_plane_check(plane, n_tiles, n_elems)) return rc;
     if (!place && n_tiles > 0) return dswx_fail(DSWX_ERR_ARG, "place is NULL");
-    bool any = out->last || out->last_index || out->share;
-    for (int k = 0; k < DSWX_STACK_MAX_CATS; ++k) {
-        if (out->count[k] && k >= spec->n_cats)
-            return dswx_fail(DSWX_ERR_ARG, "count[%d] is not NULL but n_cats is %d", k, spec->n_cats);
-        any = any || out->count[k];
-    }
-    if (!any) return dswx_fail(DSWX_ERR_ARG, "every output is NULL");
-    if (align) {
-        for (int k = 0; k < DSWX_STACK_MAX_CATS; ++k)
-            if (!aligned_to(out->count[k], 2)) return dswx_fail(DSWX_ERR_ALIGN, "count[%d] not 2-byte aligned", k);
-        if (!aligned_to(out->last_index, 2)) return dswx_fail(DSWX_ERR_ALIGN, "last_index not 2-byte aligned");
-        if (!aligned_to(place, 4)) return dswx_fail(DSWX_ERR_ALIGN, "place not 4-byte aligned");
-    }
+    if (int rc = stack_out_check(out, spec->n_cats, align)) return rc;
+    if (align && !aligned_to(place, 4)) return dswx_fail(DSWX_ERR_ALIGN, "place not 4-byte aligned");
     return DSWX_OK;
 }
 
@@ -400,7 +309,7 @@ int dswx_mosaic_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_mosaic_sp
                        int64_t width, int64_t stride, const int32_t* place, int64_t canvas_h, int64_t canvas_w,
                        const dswx_stack_out_t* out, hipStream_t s) {
     if (canvas_h == 0 || canvas_w == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     const unsigned long long nbx = ((unsigned long long)canvas_w + MOSAIC_COLS - 1) / MOSAIC_COLS;
@@ -418,18 +327,12 @@ int dswx_mosaic_launch(dswx_ctx* ctx, const uint8_t* plane, const dswx_mosaic_sp
     a.canvas_h = (int)canvas_h;
     a.canvas_w = (int)canvas_w;
     a.nbx = (unsigned)nbx;
-    a.n_cats = spec->n_cats;
-    a.fill = spec->fill;
     a.outside = spec->outside;
     a.neutral = -1;
     for (int b = 255; b >= 0; --b)
         if (spec->cat_of_byte[b] >= spec->n_cats) a.neutral = b;
-    for (int k = 0; k < DSWX_STACK_MAX_CATS; ++k) a.count[k] = out->count[k];
-    a.last = out->last;
-    a.last_index = out->last_index;
-    a.share = out->share;
-    std::memcpy(a.cat_of_byte, spec->cat_of_byte, 256);
-    const bool latest = out->last || out->last_index;
+    stack_core_args(a.c, out, spec->n_cats, spec->fill, spec->cat_of_byte);
+    const bool latest = stack_wants_latest(out);
     const unsigned gx = (unsigned)(nbx * nby);
     const bool tiny = height * width < MOSAIC_PPT;      // no 16-byte load fits into a tile: the byte-by-byte instantiation
     if (latest && tiny) hipLaunchKernelGGL((dswx_mosaic_k<true, true>), dim3(gx), dim3(MOSAIC_BLOCK), 0, s, a);
@@ -465,7 +368,7 @@ int dswx_mosaic_host(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64
                 covered[i] = false;
             }
             for (int64_t t = 0; t < n_tiles; ++t) {
-                const int64_t r = Y - get_i32(place, 2 * t), q0 = get_i32(place, 2 * t + 1);
+                const int64_t r = Y - dswx_load<int32_t>(place, (size_t)(2 * t)), q0 = dswx_load<int32_t>(place, (size_t)(2 * t + 1));
                 if (r < 0 || r >= height) continue;
                 const int64_t xa = q0 > X0 ? q0 : X0, xb = q0 + width < X0 + n ? q0 + width : X0 + n;
                 const uint8_t* row = plane + (size_t)t * (size_t)stride + (size_t)(r * width);
@@ -476,13 +379,8 @@ int dswx_mosaic_host(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64
                 }
             }
             const int64_t e0 = Y * canvas_w + X0;
-            for (int64_t i = 0; i < n; ++i) {
-                for (int k = 0; k < DSWX_STACK_MAX_CATS; ++k)
-                    if (out->count[k]) put_u16(out->count[k], e0 + i, stack_count(acc[i], k));
-                if (out->last) out->last[e0 + i] = (uint8_t)(covered[i] ? stack_last(latest[i]) : (unsigned)spec->outside);
-                if (out->last_index) put_u16(out->last_index, e0 + i, stack_last_index(latest[i]));
-                if (out->share) out->share[e0 + i] = (uint8_t)stack_share(acc[i]);
-            }
+            for (int64_t i = 0; i < n; ++i)
+                stack_put_pixel(out, e0 + i, acc[i], latest[i], covered[i] ? stack_last(latest[i]) : (unsigned)spec->outside);
         }
     return DSWX_OK;
 }
@@ -491,10 +389,9 @@ int dswx_mosaic_device(dswx_ctx_t* ctx, const uint8_t* plane, const dswx_mosaic_
                        int64_t width, int64_t stride, const int32_t* place, int64_t canvas_h, int64_t canvas_w,
                        const dswx_stack_out_t* out, void* stream) {
     if (int rc = dswx_mosaic_check(plane, spec, n_tiles, height, width, &stride, place, canvas_h, canvas_w, out, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_mosaic_launch(ctx, plane, spec, n_tiles, height, width, stride, place, canvas_h, canvas_w, out,
-                              dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) {
+        return dswx_mosaic_launch(ctx, plane, spec, n_tiles, height, width, stride, place, canvas_h, canvas_w, out, s);
+    });
 }
 
 }  // extern "C"

@@ -512,14 +512,8 @@ __global__ __launch_bounds__(OUT_BLOCK) void dswx_outline_finish_k(const Outline
 // unaligned host accesses (a host buffer may sit at any address)
 struct HostIds {
     const unsigned char* p;
-    inline uint32_t operator()(uint64_t i) const {
-        uint32_t v;
-        std::memcpy(&v, p + (size_t)i * 4, 4);
-        return v;
-    }
+    inline uint32_t operator()(uint64_t i) const { return dswx_load<uint32_t>(p, (size_t)i); }
 };
-inline void put_u32(void* base, size_t word, uint32_t v) { std::memcpy(static_cast<unsigned char*>(base) + word * 4, &v, 4); }
-inline void put_u64(void* base, size_t byte, uint64_t v) { std::memcpy(static_cast<unsigned char*>(base) + byte, &v, 8); }
 
 // The checks that the entries share, in the house order: the arguments before any context, nothing written by a refused
 // call.  `device`: the alignments, and the working memory.
@@ -558,7 +552,7 @@ int outline_check(const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t 
 int dswx_outline_launch(dswx_ctx* ctx, const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height,
                         int64_t width, const dswx_outline_out_t* out, void* work, hipStream_t s) {
     if (n_tiles == 0) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     OutlineArgs a = {};
@@ -655,7 +649,7 @@ int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int6
                     do {
                         const int64_t q = e.y * width + e.x;
                         todo[(size_t)q] = (unsigned char)(todo[(size_t)q] & ~(1u << e.d));
-                        if (chain) put_u32(chain, (size_t)at, (uint32_t)(4 * q) + e.d);
+                        if (chain) dswx_store<uint32_t>(chain, (size_t)at, (uint32_t)(4 * q) + e.d);
                         ++at;
                         area2 += outline_area2(e.x, e.y, e.d);
                         const OutlineEdge f = outline_succ(get, e.x, e.y, e.d, width, height, v, spec->connectivity);
@@ -664,12 +658,12 @@ int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int6
                     } while ((e.y * width + e.x != p || e.d != d0) && at < E);   // (the map is a bijection: `at` never gets there)
                     if (rings && R < (uint64_t)max_rings) {
                         unsigned char* const row = rings + (size_t)R * DSWX_OUTLINE_ROW_WORDS * 4;
-                        put_u32(row, OUTLINE_ID, v);
-                        put_u32(row, OUTLINE_START, (uint32_t)(4 * p) + d0);
-                        put_u32(row, OUTLINE_OFFSET, (uint32_t)offset);
-                        put_u32(row, OUTLINE_LENGTH, (uint32_t)(at - offset));
-                        put_u32(row, OUTLINE_CORNERS, corners);
-                        put_u64(row, OUTLINE_AREA2 * 4, (uint64_t)area2);
+                        dswx_store<uint32_t>(row, OUTLINE_ID, v);
+                        dswx_store<uint32_t>(row, OUTLINE_START, (uint32_t)(4 * p) + d0);
+                        dswx_store<uint32_t>(row, OUTLINE_OFFSET, (uint32_t)offset);
+                        dswx_store<uint32_t>(row, OUTLINE_LENGTH, (uint32_t)(at - offset));
+                        dswx_store<uint32_t>(row, OUTLINE_CORNERS, corners);
+                        dswx_store<uint64_t>(row + OUTLINE_AREA2 * 4, 0, (uint64_t)area2);
                     }
                     ++R;
                     head[OUTLINE_HEAD_OUTER] += area2 > 0;
@@ -681,7 +675,7 @@ int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int6
             head[OUTLINE_HEAD_WRITTEN] = E;
         }
         if (out->head)
-            for (int w = 0; w < DSWX_OUTLINE_HEAD_WORDS; ++w) put_u64(out->head, (size_t)(t * DSWX_OUTLINE_HEAD_WORDS + w) * 8, head[w]);
+            for (int w = 0; w < DSWX_OUTLINE_HEAD_WORDS; ++w) dswx_store<uint64_t>(out->head, (size_t)(t * DSWX_OUTLINE_HEAD_WORDS + w), head[w]);
     }
     return DSWX_OK;
 }
@@ -689,9 +683,7 @@ int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int6
 int dswx_outline_device(dswx_ctx_t* ctx, const uint32_t* ids, const dswx_outline_spec_t* spec, int64_t n_tiles, int64_t height,
                         int64_t width, const dswx_outline_out_t* out, void* work_device, uint64_t work_bytes, void* stream) {
     if (int rc = outline_check(ids, spec, n_tiles, height, width, out, true, work_device, work_bytes)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_outline_launch(ctx, ids, spec, n_tiles, height, width, out, work_device, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) { return dswx_outline_launch(ctx, ids, spec, n_tiles, height, width, out, work_device, s); });
 }
 
 }  // extern "C"

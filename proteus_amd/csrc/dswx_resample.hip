@@ -253,7 +253,7 @@ void resample_host_tiles(const unsigned char* src, const dswx_resample_spec_t* s
         for (int64_t Y = 0; Y < dst_h; ++Y)
             for (int64_t X = 0; X < dst_w; ++X) {
                 int64_t sx, sy;
-                mesh_position([&](int64_t k) { return mesh_node_at(mesh, m0 + k); }, s, mesh_w, X, Y, &sx, &sy);
+                mesh_position([&](int64_t k) { return dswx_load<int32_t>(mesh, (size_t)(m0 + k)); }, s, mesh_w, X, Y, &sx, &sy);
                 const ResamplePixel px = resample_pixel(spec->method == DSWX_RESAMPLE_CUBIC, sx, sy, [&](int64_t c, int64_t r) {
                     if (c < 0 || c >= width || r < 0 || r >= height) return resample_no_tap();
                     uint32_t raw = 0;
@@ -299,34 +299,33 @@ int dswx_resample_device(dswx_ctx_t* ctx, const void* plane, const dswx_resample
                          int64_t width, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out, void* stream) {
     int64_t stride;
     if (int rc = resample_check(plane, spec, n_tiles, height, width, mesh, dst_h, dst_w, out, &stride, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->how || out->head)) {
-        ctx->last_kernel = "none (empty input)";
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) -> int {
+        if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->how || out->head)) {
+            ctx->last_kernel = DSWX_NO_KERNEL;
+            return DSWX_OK;
+        }
+        const bool f32 = spec->kind == DSWX_RESAMPLE_F32;
+        ResArgs a = {};
+        unsigned gy;
+        if (int rc = dswx_mesh_launch_prepare(a, plane, stride, f32 ? 4 : 2, mesh, spec->mesh_tile_stride_nodes, spec->shift, n_tiles, height, width,
+                                              dst_h, dst_w, RES_RECT_H, RES_RECT_W, out->dst, out->head, s, &gy))
+            return rc;
+        a.cubic = spec->method == DSWX_RESAMPLE_CUBIC;
+        a.has_nodata = spec->has_nodata != 0;
+        a.nodata = spec->nodata;
+        a.outside = spec->outside;
+        a.how = out->how;
+        const unsigned gx = (unsigned)(a.n_rects < RES_MAX_GRID_X ? a.n_rects : RES_MAX_GRID_X);
+        const dim3 grid(gx, gy), block(RES_BLOCK);
+        if (f32) hipLaunchKernelGGL((dswx_resample_k<true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((dswx_resample_k<false>), grid, block, 0, s, a);
+        HIP_TRY(hipGetLastError());
+        char info[256];
+        snprintf(info, sizeof info, "dswx_resample_k grid=(%u,%u,1) block=%d rect=%dx%d lds_elems=%d kind=%s method=%s shift=%d head=%d", gx, gy,
+                 RES_BLOCK, RES_RECT_H, RES_RECT_W, RES_LDS, f32 ? "f32" : "i16", a.cubic ? "cubic" : "bilinear", spec->shift, out->head ? 1 : 0);
+        ctx->last_kernel = info;
         return DSWX_OK;
-    }
-    hipStream_t s = dswx_stream_of(ctx, stream);
-    const bool f32 = spec->kind == DSWX_RESAMPLE_F32;
-    ResArgs a = {};
-    unsigned gy;
-    if (int rc = dswx_mesh_launch_prepare(a, plane, stride, f32 ? 4 : 2, mesh, spec->mesh_tile_stride_nodes, spec->shift, n_tiles, height, width,
-                                          dst_h, dst_w, RES_RECT_H, RES_RECT_W, out->dst, out->head, s, &gy))
-        return rc;
-    a.cubic = spec->method == DSWX_RESAMPLE_CUBIC;
-    a.has_nodata = spec->has_nodata != 0;
-    a.nodata = spec->nodata;
-    a.outside = spec->outside;
-    a.how = out->how;
-    const unsigned gx = (unsigned)(a.n_rects < RES_MAX_GRID_X ? a.n_rects : RES_MAX_GRID_X);
-    const dim3 grid(gx, gy), block(RES_BLOCK);
-    if (f32) hipLaunchKernelGGL((dswx_resample_k<true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((dswx_resample_k<false>), grid, block, 0, s, a);
-    HIP_TRY(hipGetLastError());
-    char info[256];
-    snprintf(info, sizeof info, "dswx_resample_k grid=(%u,%u,1) block=%d rect=%dx%d lds_elems=%d kind=%s method=%s shift=%d head=%d", gx, gy,
-             RES_BLOCK, RES_RECT_H, RES_RECT_W, RES_LDS, f32 ? "f32" : "i16", a.cubic ? "cubic" : "bilinear", spec->shift, out->head ? 1 : 0);
-    ctx->last_kernel = info;
-    return DSWX_OK;
+    });
 }
 
 }  // extern "C"

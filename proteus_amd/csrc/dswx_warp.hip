@@ -390,7 +390,7 @@ int dswx_warp_check(const void* plane, const dswx_warp_spec_t* spec, int64_t n_t
 int dswx_warp_launch(dswx_ctx* ctx, const void* plane, const dswx_warp_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                      int64_t src_stride, const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, hipStream_t s) {
     if (!dswx_mesh_work(n_tiles, dst_h, dst_w, out->dst || out->src_index || out->head)) {
-        ctx->last_kernel = "none (empty input)";
+        ctx->last_kernel = DSWX_NO_KERNEL;
         return DSWX_OK;
     }
     const int eb = spec->elem_bytes;
@@ -438,7 +438,7 @@ int dswx_warp_host(const void* plane, const dswx_warp_spec_t* spec, int64_t n_ti
         for (int64_t Y = 0; Y < dst_h; ++Y)
             for (int64_t X = 0; X < dst_w; ++X) {
                 int64_t sx, sy;
-                mesh_position([&](int64_t k) { return mesh_node_at(mesh, m0 + k); }, s, mesh_w, X, Y, &sx, &sy);
+                mesh_position([&](int64_t k) { return dswx_load<int32_t>(mesh, (size_t)(m0 + k)); }, s, mesh_w, X, Y, &sx, &sy);
                 const int64_t c = sx >> 8, r = sy >> 8;
                 const bool in = c >= 0 && c < width && r >= 0 && r < height;
                 const int64_t e = t * dst_h * dst_w + Y * dst_w + X;
@@ -466,9 +466,9 @@ int dswx_warp_device(dswx_ctx_t* ctx, const void* plane, const dswx_warp_spec_t*
                      const int32_t* mesh, int64_t dst_h, int64_t dst_w, const dswx_warp_out_t* out, void* stream) {
     int64_t stride;
     if (int rc = dswx_warp_check(plane, spec, n_tiles, height, width, mesh, dst_h, dst_w, out, &stride, true)) return rc;
-    if (!ctx) return dswx_fail(DSWX_ERR_ARG, "ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    return dswx_warp_launch(ctx, plane, spec, n_tiles, height, width, stride, mesh, dst_h, dst_w, out, dswx_stream_of(ctx, stream));
+    return dswx_device_entry(ctx, stream, [&](hipStream_t s) {
+        return dswx_warp_launch(ctx, plane, spec, n_tiles, height, width, stride, mesh, dst_h, dst_w, out, s);
+    });
 }
 
 }  // extern "C"

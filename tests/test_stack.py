@@ -4,6 +4,7 @@ value, every n_cats, tile counts and sizes either side of the kernel's units, st
 addresses; 65535 tiles whose packed counts must not carry; every refusal that needs no device; the header; the struct
 mirrors; the WTR specs written out by hand; the C example."""
 import ctypes
+import json
 import os
 import shutil
 import subprocess
@@ -293,6 +294,34 @@ def test_refusals_that_need_no_device():
                 lambda: _capi.stack_host(tiles, good, want=('median',)), lambda: _capi.stack_host(tiles, good, want=())):
         with pytest.raises(ValueError):
             bad()
+
+
+def test_stack_and_mosaic_host_entries_under_asan_and_ubsan_in_a_program_of_their_own():
+    """tests/native/stack_host_san.cpp with proteus_amd/csrc/dswx_stack.hip and dswx_mosaic.hip compiled into it, host code under
+    ASan + UBSan: 0, 1 and 9 tiles of 0, 15, 16 and 33 elements, and three tiles of 3 x 5 and 1 x 1 hanging over every side of a
+    7 x 20 canvas (INT32_MIN and INT32_MAX among the placements), on heap blocks of exactly the bytes the entries may touch, at
+    odd addresses.  A child process; nothing is loaded into this interpreter."""
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        pytest.skip('needs hipcc')
+    out_dir = os.path.join(ROOT, 'tests', 'native', '_build')
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, 'stack_host_san')
+    csrc = os.path.join(ROOT, 'proteus_amd', 'csrc')
+    cmd = [hipcc, '--offload-arch=gfx950', '-std=c++17', '-g', '-O1', '-ffp-contract=off', '-Wall', '-Wno-unused-function',
+           '-Xarch_host', '-fsanitize=address,undefined', '-Xarch_host', '-fno-sanitize-recover=undefined',
+           '-I', os.path.join(ROOT, 'include'), '-I', csrc, os.path.join(ROOT, 'tests', 'native', 'stack_host_san.cpp'),
+           os.path.join(csrc, 'dswx_stack.hip'), os.path.join(csrc, 'dswx_mosaic.hip'), '-o', exe]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    if res.returncode != 0 and 'libclang_rt.asan' in res.stderr:     # (only the runtime: an error in the sources must fail)
+        pytest.skip(f'sanitizer runtime missing: {res.stderr[-300:]}')
+    assert res.returncode == 0, res.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:halt_on_error=1', UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1')
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert res.returncode == 0, (res.stdout[-1000:], res.stderr[-4000:])
+    assert 'ERROR: AddressSanitizer' not in res.stderr and 'runtime error' not in res.stderr and 'LeakSanitizer' not in res.stderr
+    out = json.loads(res.stdout.strip().splitlines()[-1])
+    assert out['failures'] == 0 and out['cases'] == 143
 
 
 def test_header_says_has_stack_and_abi_7():
