@@ -1498,6 +1498,78 @@ int dswx_resample_device(dswx_ctx_t* ctx, const void* plane, const dswx_resample
 int dswx_resample_host(const void* plane, const dswx_resample_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
                        const int32_t* mesh_host, int64_t dst_h, int64_t dst_w, const dswx_resample_out_t* out_host);
 
+/* ---- land mesh: the LAND layer from land-cover maps that are NOT on the HLS grid, read through two meshes (additive to ABI v7)
+ * dswx_landcover_mask_* wants the ESA WorldCover map on the grid three times finer than the HLS grid and the Copernicus
+ * CGLS-100 m map on the HLS grid.  Both ship in EPSG:4326.  Chaining dswx_warp_device twice and dswx_landcover_mask_device
+ * needs a [3 height][3 width] and a [height][width] intermediate per tile and writes 10 bytes per HLS pixel only to read them
+ * again.  These entries read the two SOURCE windows through their meshes and write LAND, and are defined as exactly that chain.
+ * A C caller tests for them with DSWX_HAS_LAND_MESH.
+ * STILL REFUSED: mode or average resampling; a projection on the device (proteus_amd/landmesh.py plans the windows and makes
+ * the meshes on the host); the antimeridian; mosaics of several files per map.
+ * UNPINNED: GDAL and PROJ are not part of this project's environment, so gdal.Warp's own choice of the nearest pixel, its
+ * approximate transformer (0.125 pixel error threshold) and its handling of a centre exactly on a pixel boundary are not
+ * pinned by any test.  The definition below is this project's own.
+ * THE DEFINITION, by reference to the two sections it joins.  For every tile
+ *                  land == dswx_landcover_mask(W3, CG, forest_classes, thresholds, year_offset)
+ *   W3         uint8 [3 height][3 width]: the `dst` of dswx_warp_* (elem_bytes 1) of the WorldCover plane -- tiles of wc_h x wc_w,
+ *              wc_tile_stride apart -- through mesh_wc with shift_wc and outside_wc onto a destination of 3 height x 3 width.
+ *   CG         uint8 [height][width]: the `dst` of dswx_warp_* of the CGLS plane -- tiles of cg_h x cg_w, cg_tile_stride apart --
+ *              through mesh_cg with shift_cg and outside_cg onto a destination of height x width.
+ *   MESHES     as in the "warp" section, one per map: mesh_wc has ((3 height + step - 1) >> shift_wc) + 1 rows of nodes,
+ *              mesh_cg ((height + step - 1) >> shift_cg) + 1, columns likewise.  ANY CONTENT IS LEGAL, INT32_MIN and INT32_MAX
+ *              included.  The POSITION of a pixel is the one of that section and no other.
+ *   land       uint8 [n_tiles][land_tile_stride], the first height * width bytes of every tile written, the rest untouched:
+ *              the 3 x 3 counts of W3, the forest test of CG, the hierarchy and the uint8 wrap of the two developed classes
+ *              exactly as dswx_landcover_mask_* state them.  NULL = not wanted.
+ *   head       uint64 [n_tiles][DSWX_LAND_MESH_HEAD_WORDS]: word 0 the HLS pixels, 1 the fine pixels whose WorldCover tap was
+ *              inside, 2 those whose tap was outside, 3 the HLS pixels whose CGLS tap was inside, 4 those whose tap was outside,
+ *              5 the HLS pixels whose nine WorldCover taps were ALL outside, 6 the LAND pixels equal to 255, 7 zero.  NULL =
+ *              not wanted.  (Words 2 and 4 not zero: a map does not cover the tile.)
+ * height * width <= 2^30 / 9 (the fine lattice stays within the warp's limit) and wc_h * wc_w, cg_h * cg_w <= 2^30.  n_tiles ==
+ * 0 or an empty lattice writes nothing; an empty source raster makes every tap `outside`.  Integer arithmetic only: the result
+ * does not depend on the launch geometry, and the atomics of `head` (additions) commute. */
+#define DSWX_HAS_LAND_MESH 1
+#define DSWX_LAND_MESH_HEAD_WORDS 8
+typedef struct dswx_land_mesh_spec {
+    int32_t  shift_wc;                     /* 0 .. DSWX_WARP_MAX_SHIFT: a node of mesh_wc every 1 << shift_wc FINE pixels */
+    int32_t  shift_cg;                     /* 0 .. DSWX_WARP_MAX_SHIFT: a node of mesh_cg every 1 << shift_cg HLS pixels */
+    uint32_t outside_wc;                   /* 0 .. 255: the WorldCover byte of a tap that is not inside */
+    uint32_t outside_cg;                   /* 0 .. 255: the CGLS byte of a tap that is not inside */
+    int32_t  thresholds[4];                /* as dswx_landcover_mask_*: evergreen, low- and high-intensity developed, water */
+    int32_t  year_offset;                  /* as dswx_landcover_mask_* */
+    int32_t  n_forest_classes;             /* >= 0 */
+    int32_t  reserved;                     /* must be 0 */
+    int32_t  reserved2;                    /* must be 0 (padding in front of the pointer) */
+    const int32_t* forest_classes;         /* HOST memory, read before the call returns; NULL only with n_forest_classes 0 */
+    int64_t  wc_tile_stride;               /* bytes between the tiles of the WorldCover plane; 0 = wc_h * wc_w */
+    int64_t  cg_tile_stride;               /* bytes between the tiles of the CGLS plane; 0 = cg_h * cg_w */
+    int64_t  mesh_wc_tile_stride_nodes;    /* nodes between the meshes of consecutive tiles; 0 = one mesh for all tiles */
+    int64_t  mesh_cg_tile_stride_nodes;    /* likewise */
+    int64_t  land_tile_stride;             /* bytes between the LAND rasters of consecutive tiles; 0 = height * width (the
+                                              LAND plane of a resident batch: dswx_batch_geom_t.tile_stride) */
+} dswx_land_mesh_spec_t;                   /* 96 bytes */
+/* The two planes and the two meshes in DEVICE memory -> land and head (device memory).  Asynchronous on `stream` (NULL = the
+ * context's stream): one hipMemsetAsync of `head` (only if wanted) and ONE kernel launch, whatever the tile count (past the
+ * 65535 tiles of grid.y the workgroups walk the tiles); no synchronisation, no scratch of the context, no allocation, nothing
+ * the caller has to zero in front: a second call on the same outputs gives the same bytes, and no workgroup ever waits for
+ * another.  Refusals, in the order and with the texts of dswx_warp_device and dswx_landcover_mask_*: a NULL spec, a shift
+ * outside 0 .. 8, reserved or reserved2 != 0, outside_wc or outside_cg above 255, a negative forest count or a NULL list with a
+ * positive one (the thresholds are part of the spec and cannot be NULL), height * width above 2^30 / 9; per map (WorldCover
+ * first) a negative size, tile count or stride, a source above 2^30 pixels, a stride that is neither 0 nor large enough, more
+ * than 2^32 tiles or a plane above 2^46 bytes; a land_tile_stride that is neither 0 nor at least height * width; with something
+ * to write (land or head), a NULL mesh or a NULL plane whose raster is not empty: DSWX_ERR_ARG.  A mesh off 4 bytes or
+ * head off 8: DSWX_ERR_ALIGN (the planes and land are bytes).  The arguments are checked before the context is, and a refused
+ * call writes nothing.  land and head both NULL is no work, not an error.  Overlap is NOT CHECKED. */
+int dswx_land_mesh_device(dswx_ctx_t* ctx, const uint8_t* worldcover, int64_t wc_h, int64_t wc_w, const uint8_t* copernicus,
+                          int64_t cg_h, int64_t cg_w, const dswx_land_mesh_spec_t* spec, int64_t n_tiles, int64_t height,
+                          int64_t width, const int32_t* mesh_wc_device, const int32_t* mesh_cg_device, uint8_t* land,
+                          uint64_t* head, void* stream);
+/* The same definition on HOST buffers in plain scalar C++, with HOST meshes: needs no device and no context.  The other half of
+ * a comparison, not a fallback.  The refusals of dswx_land_mesh_device, except that every buffer may sit at any address. */
+int dswx_land_mesh_host(const uint8_t* worldcover, int64_t wc_h, int64_t wc_w, const uint8_t* copernicus, int64_t cg_h,
+                        int64_t cg_w, const dswx_land_mesh_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                        const int32_t* mesh_wc_host, const int32_t* mesh_cg_host, uint8_t* land, uint64_t* head);
+
 /* ---- device plumbing for hosts without another HIP binding ------------------- */
 int dswx_device_malloc(dswx_ctx_t* ctx, size_t bytes, void** out);
 int dswx_device_free(dswx_ctx_t* ctx, void* ptr);
@@ -1526,7 +1598,7 @@ int dswx_event_record(dswx_ctx_t* ctx, void* event, void* stream);
 int dswx_event_elapsed_ms(dswx_ctx_t* ctx, void* start, void* stop, float* ms);
 
 /* Name and launch geometry of the kernel the last dswx_classify_* / dswx_*checksum* / dswx_*compare* / dswx_*histogram* /
- * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* / dswx_*warp* / dswx_*resample* call on this context selected (for profiles / DESIGN.md; the
+ * dswx_*crosstab* / dswx_*stack* / dswx_*grid* / dswx_*label* / dswx_*body_table* / dswx_*distance* / dswx_*outline* / dswx_*burn* / dswx_*mosaic* / dswx_*warp* / dswx_*resample* / dswx_land_mesh_device call on this context selected (for profiles / DESIGN.md; the
  * histogram's, the crosstab's, the stack's and the grid's also name their replica count): writes a NUL-terminated string. */
 int dswx_last_kernel_info(dswx_ctx_t* ctx, char* buf, size_t buflen);
 

@@ -51,7 +51,8 @@ EXPORTED_SYMBOLS = (
     'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host',
     'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host',
     'dswx_warp_device', 'dswx_batch_warp', 'dswx_warp_host',
-    'dswx_resample_device', 'dswx_resample_host')
+    'dswx_resample_device', 'dswx_resample_host',
+    'dswx_land_mesh_device', 'dswx_land_mesh_host')
 HAS_COMPARE = 1                   # DSWX_HAS_COMPARE: additive to ABI v7
 CMP_U8, CMP_U16, CMP_I16, CMP_F32, CMP_F64 = range(5)
 HAS_HISTOGRAM = 1                 # DSWX_HAS_HISTOGRAM: additive to ABI v7
@@ -97,6 +98,10 @@ RESAMPLE_HEAD_WORDS, RESAMPLE_F32, RESAMPLE_I16, RESAMPLE_BILINEAR, RESAMPLE_CUB
 # csrc/dswx_resample_rule.h: the rows and the columns of the destination rectangle of one workgroup and the elements of the
 # source window that it stages in LDS (a larger source box gathers from global memory; tests build shapes around the seams)
 RESAMPLE_RECT_H, RESAMPLE_RECT_W, RESAMPLE_LDS_ELEMS = 8, 32, 4096
+HAS_LAND_MESH = 1                 # DSWX_HAS_LAND_MESH: additive to ABI v7
+LAND_MESH_HEAD_WORDS = 8
+# csrc/dswx_land_mesh.hip: the rows and the columns of the rectangle of HLS pixels of one workgroup (tests build shapes around the seams)
+LAND_MESH_RECT_H, LAND_MESH_RECT_W = 8, 32
 
 
 class DswxError(RuntimeError):
@@ -267,6 +272,26 @@ class ResampleOut(ctypes.Structure):
     @classmethod
     def of(cls, dst=None, how=None, head=None):
         return cls(dst or None, how or None, head or None)
+
+
+class LandMeshSpec(ctypes.Structure):
+    """dswx_land_mesh_spec_t; proteus_amd.landmesh.Spec is the Python form.  `forest` keeps the list that the pointer names."""
+    _fields_ = [('shift_wc', ctypes.c_int32), ('shift_cg', ctypes.c_int32), ('outside_wc', ctypes.c_uint32), ('outside_cg', ctypes.c_uint32),
+                ('thresholds', ctypes.c_int32 * 4), ('year_offset', ctypes.c_int32), ('n_forest_classes', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('forest_classes', ctypes.c_void_p),
+                ('wc_tile_stride', ctypes.c_int64), ('cg_tile_stride', ctypes.c_int64), ('mesh_wc_tile_stride_nodes', ctypes.c_int64),
+                ('mesh_cg_tile_stride_nodes', ctypes.c_int64), ('land_tile_stride', ctypes.c_int64)]
+
+    @classmethod
+    def of(cls, spec):
+        fc = np.ascontiguousarray(list(spec.forest_classes or []), dtype=np.int32)
+        c = cls(int(spec.shift_wc), int(spec.shift_cg), int(spec.outside_wc) & 0xFFFFFFFF, int(spec.outside_cg) & 0xFFFFFFFF,
+                (ctypes.c_int32 * 4)(*[int(v) for v in spec.thresholds]), int(spec.year_offset), int(fc.size),
+                int(getattr(spec, 'reserved', 0)), int(getattr(spec, 'reserved2', 0)), fc.ctypes.data if fc.size else None,
+                int(spec.wc_tile_stride), int(spec.cg_tile_stride), int(spec.mesh_wc_tile_stride_nodes),
+                int(spec.mesh_cg_tile_stride_nodes), int(spec.land_tile_stride))
+        c.forest = fc
+        return c
 
 
 class GridSpec(ctypes.Structure):
@@ -581,6 +606,8 @@ def load_library(path=None):
         'dswx_warp_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
         'dswx_resample_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, i64, i64, vp, vp]),
         'dswx_resample_host': (ctypes.c_int, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
+        'dswx_land_mesh_device': (ctypes.c_int, [vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp, vp]),
+        'dswx_land_mesh_host': (ctypes.c_int, [vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, vp, vp, vp, vp]),
         'dswx_grid_device': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, i64, vp, vp]),
         'dswx_batch_grid': (ctypes.c_int, [vp, ctypes.c_int32, vp, i64, i64, vp, vp]),
         'dswx_grid_host': (ctypes.c_int, [vp, vp, i64, i64, i64, i64, vp]),
@@ -1250,6 +1277,43 @@ class Context:
                                              int(height), int(width), ctypes.c_void_p(mesh_ptr), int(dst_h), int(dst_w),
                                              ctypes.byref(out), _stream_arg(stream)))
 
+    def land_mesh_device(self, wc_ptr, wc_shape, cg_ptr, cg_shape, spec, n_tiles, height, width, mesh_wc_ptr, mesh_cg_ptr,
+                         land_ptr=None, head_ptr=None, stream=None):
+        """dswx_land_mesh_device: the LAND layer of n_tiles tiles of height x width HLS pixels from the device planes uint8
+        [n_tiles][wc_shape] (WorldCover) and [n_tiles][cg_shape] (CGLS) read through the device meshes at mesh_wc_ptr (of the
+        lattice 3 height x 3 width) and mesh_cg_ptr by `spec` (a landmesh.Spec; include/dswx_hip.h "land mesh",
+        proteus_amd/landmesh.py states the definition in numpy) -> land uint8 [n_tiles][spec.land_tile_stride or height *
+        width] and head uint64 [n_tiles][8], each wanted iff its address is given; one memset of the head and ONE launch,
+        asynchronous."""
+        _check(self.lib.dswx_land_mesh_device(self.handle, ctypes.c_void_p(wc_ptr), int(wc_shape[0]), int(wc_shape[1]),
+                                              ctypes.c_void_p(cg_ptr), int(cg_shape[0]), int(cg_shape[1]),
+                                              ctypes.byref(LandMeshSpec.of(spec)), int(n_tiles), int(height), int(width),
+                                              ctypes.c_void_p(mesh_wc_ptr), ctypes.c_void_p(mesh_cg_ptr),
+                                              ctypes.c_void_p(land_ptr or None), ctypes.c_void_p(head_ptr or None), _stream_arg(stream)))
+
+    def land_mesh(self, worldcover, copernicus, mesh_wc, mesh_cg, shape, spec):
+        """Host arrays in, host arrays out: the uint8 source windows [wc_h, wc_w] and [cg_h, cg_w] of ONE tile and their int32
+        meshes uploaded, dswx_land_mesh_device, (land uint8 [H, W], head uint64 [8]) downloaded; complete on return."""
+        H, W = (int(v) for v in shape)
+        arrays = [np.ascontiguousarray(worldcover, dtype=np.uint8), np.ascontiguousarray(copernicus, dtype=np.uint8),
+                  np.ascontiguousarray(mesh_wc, dtype=np.int32), np.ascontiguousarray(mesh_cg, dtype=np.int32)]
+        bufs = []
+        try:
+            for a in arrays:
+                bufs.append(self.malloc(max(a.nbytes, 8)))
+                if a.nbytes:
+                    bufs[-1].upload(a)
+            out = self.malloc(max(H * W, 1) + 8 * LAND_MESH_HEAD_WORDS + 8)
+            bufs.append(out)
+            head_at = -(-max(H * W, 1) // 8) * 8
+            self.land_mesh_device(bufs[0].ptr, arrays[0].shape, bufs[1].ptr, arrays[1].shape, spec, 1, H, W, bufs[2].ptr, bufs[3].ptr,
+                                  out.ptr, out.ptr + head_at)
+            self.synchronize()
+            return out.download(np.uint8, H * W).reshape(H, W), out.download(np.uint64, LAND_MESH_HEAD_WORDS, offset=head_at)
+        finally:
+            for b in bufs:
+                b.free()
+
     def grid_device(self, plane_ptr, spec, n_tiles, height, width, out, tile_stride=0, stream=None):
         """dswx_grid_device: one device plane uint8 [n_tiles][tile_stride], every tile a height x width raster, aggregated
         onto cells by `spec` (a grid.Spec; include/dswx_hip.h "grid", proteus_amd/grid.py states the definition in numpy) ->
@@ -1534,6 +1598,43 @@ def resample_host(tiles, mesh, spec, dst_shape, want=('dst', 'how', 'head'), ras
     raster=(H, W), `tiles` is a padded plane [n_tiles, spec.src_tile_stride] whose padding is not read."""
     return _mesh_host('dswx_resample_host', _resample_planes, ResampleSpec, ResampleOut, tiles, lambda dt: dt == spec.dtype,
                       spec.dtype, mesh, spec, dst_shape, want, raster)
+
+
+def land_mesh_host(worldcover, copernicus, mesh_wc, mesh_cg, spec, shape, want=('land', 'head'), wc_raster=None, cg_raster=None,
+                   land=None):
+    """dswx_land_mesh_host (no device needed): the outputs of proteus_amd.landmesh.land_tiles named in `want` -- 'land' uint8
+    [n, H, W] ([n, spec.land_tile_stride] with a stride), 'head' uint64 [n, 8] -- of the host planes uint8 `worldcover` [n, wc_h,
+    wc_w] and `copernicus` [n, cg_h, cg_w] read through the int32 meshes mesh_wc (of the lattice 3 H x 3 W) and mesh_cg (of H x
+    W) by `spec` (a landmesh.Spec), by the library's scalar statement of the definition.  With wc_raster=(wc_h, wc_w) /
+    cg_raster=, the plane is padded, [n, spec.wc_tile_stride] / [n, spec.cg_tile_stride], and its padding is not read.  `land`:
+    an array to write into (what the entry does not write stays)."""
+    wc, n, wc_h, wc_w, _ = _host_plane(worldcover, wc_raster)
+    cg, n_cg, cg_h, cg_w, _ = _host_plane(copernicus, cg_raster)
+    if n_cg != n:
+        raise ValueError(f'{n} WorldCover tiles but {n_cg} CGLS tiles')
+    H, W = (int(v) for v in shape)
+    mesh_wc, mesh_cg = np.ascontiguousarray(mesh_wc, dtype=np.int32), np.ascontiguousarray(mesh_cg, dtype=np.int32)
+    if n > 0 and H > 0 and W > 0:            # the node counts that the entry itself cannot check (it has addresses, not arrays)
+        for what, mesh, s, stride, dims in (('mesh_wc', mesh_wc, spec.shift_wc, spec.mesh_wc_tile_stride_nodes, (3 * H, 3 * W)),
+                                            ('mesh_cg', mesh_cg, spec.shift_cg, spec.mesh_cg_tile_stride_nodes, (H, W))):
+            if 0 <= s <= WARP_MAX_SHIFT:
+                step = 1 << s
+                nodes = (((dims[0] + step - 1) >> s) + 1) * (((dims[1] + step - 1) >> s) + 1)
+                if mesh.size < 2 * ((n - 1) * stride + nodes):
+                    raise ValueError(f'{what} for {dims[0]} x {dims[1]} at shift {s} has {nodes} nodes per tile, {mesh.shape} is too small')
+    want = _wanted(want, {'land': 0, 'head': 0})
+    res = {}
+    if 'land' in want:
+        res['land'] = land if land is not None else np.zeros((n, spec.land_tile_stride) if spec.land_tile_stride else (n, max(H, 0), max(W, 0)),
+                                                             dtype=np.uint8)
+    if 'head' in want:
+        res['head'] = np.zeros((n, LAND_MESH_HEAD_WORDS), dtype=np.uint64)
+    _check(load_library().dswx_land_mesh_host(_host_ptr(wc) if wc.size else None, int(wc_h), int(wc_w), _host_ptr(cg) if cg.size else None,
+                                              int(cg_h), int(cg_w), ctypes.byref(LandMeshSpec.of(spec)), n, H, W,
+                                              _host_ptr(mesh_wc) if mesh_wc.size else None, _host_ptr(mesh_cg) if mesh_cg.size else None,
+                                              res['land'].ctypes.data if 'land' in res and res['land'].size else None,
+                                              res['head'].ctypes.data if 'head' in res and res['head'].size else None))
+    return res
 
 
 def _stack_planes(want, spec, shape, make):
@@ -2029,6 +2130,23 @@ class DeviceBatch:
                                                 ctypes.c_void_p(mesh_ptr), int(dst_shape[0]), int(dst_shape[1]), ctypes.byref(out),
                                                 _stream_arg(stream)))
         return res
+
+    def land_mesh(self, wc_ptr, wc_shape, cg_ptr, cg_shape, spec, mesh_wc_ptr, mesh_cg_ptr, tile0=0, n_tiles=None, head_ptr=None,
+                  stream=None):
+        """dswx_land_mesh_device straight into the LAND plane of tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from
+        tile0) of this batch, with the batch's tile stride: source tile 0 and mesh 0 belong to tile0.  `spec` is a landmesh.Spec
+        whose land_tile_stride is 0 (the batch has its own).  head_ptr: device uint64 [n_tiles][8], or None."""
+        import copy
+        if spec.land_tile_stride:
+            raise ValueError('the LAND plane has the stride of the batch: spec.land_tile_stride must be 0')
+        land = self._plane('land')[0]
+        nt = self._tiles(tile0, n_tiles)[1]
+        if tile0 < 0 or tile0 + nt > self.n_tiles:
+            raise ValueError(f'tiles {tile0} .. {tile0 + nt - 1} are not tiles of this batch of {self.n_tiles}')
+        spec = copy.copy(spec)
+        spec.land_tile_stride = self.tile_stride
+        self.ctx.land_mesh_device(wc_ptr, wc_shape, cg_ptr, cg_shape, spec, nt, self.height, self.width, mesh_wc_ptr, mesh_cg_ptr,
+                                  land + int(tile0) * self.tile_stride, head_ptr, stream)
 
     def grid(self, name, spec, tile0=0, n_tiles=None, want=('count', 'share', 'coverage', 'major'), stream=None):
         """dswx_batch_grid: tiles tile0 .. tile0 + n_tiles - 1 (default: every tile from tile0) of the uint8 plane `name`

@@ -7,6 +7,7 @@
 #include <limits>
 
 #include "dswx_host.h"
+#include "dswx_land_mesh_rule.h"
 
 // ------------------------------------------------------------------------------
 // generate_interpreted_layer (:1687-1707) on its own: DIAG in decimal (any integer,
@@ -288,16 +289,7 @@ struct LandArgs {
     int low_class, high_class;   // year_offset, 100 + year_offset (as uint8)
 };
 
-// `is_forest`: the CGLS class of the pixel is one of forest_mask_landcover_classes
-__device__ __forceinline__ int land_class(const LandArgs& a, int water, int urban, int tree, bool is_forest) {
-    if (!is_forest) tree = 0;
-    int v = 255;
-    if (tree >= a.thr_tree) v = 201;
-    if (urban >= a.thr_low) v = a.low_class;
-    if (urban >= a.thr_high) v = a.high_class;
-    if (water >= a.thr_water) v = 200;
-    return v;
-}
+// The class tests, the hierarchy (land_class) and the forest set are dswx_land_mesh_rule.h, shared with dswx_land_mesh.hip.
 
 // The nine class tests per pixel (is the byte 80 / 90 / 95, 50, 10?) are ONE 256-entry LDS table
 // lookup per WorldCover byte -- water | urban << 4 | tree << 8, so that the sum of nine entries IS the
@@ -315,7 +307,7 @@ __global__ __launch_bounds__(256) void dswx_landcover_v3(const LandArgs a) {
                                           // argument's bit set is a global load in the middle of the pixel loop)
     {
         const int v = threadIdx.x;
-        s_code[v] = (uint16_t)((((v == 80) | (v == 90) | (v == 95)) ? 1 : 0) | (v == 50 ? 16 : 0) | (v == 10 ? 256 : 0));
+        s_code[v] = (uint16_t)land_code(v);
         s_forest[v] = (uint8_t)((a.forest_bits[v >> 5] >> (v & 31)) & 1u);
     }
     __syncthreads();
@@ -756,15 +748,7 @@ static int land_check(LandArgs* a, dswx_ctx_t* ctx, const uint8_t* worldcover_up
     if (height < 0 || width < 0 || n_forest_classes < 0 || (n_forest_classes > 0 && !forest_classes))
         return dswx_fail(DSWX_ERR_ARG, "bad size");
     std::memset(a, 0, sizeof *a);
-    for (int i = 0; i < n_forest_classes; ++i) {
-        const int c = forest_classes[i];
-        if (c >= 0 && c <= 255) a->forest_bits[c >> 5] |= 1u << (c & 31);
-    }
-    a->thr_tree = thresholds[0]; a->thr_low = thresholds[1]; a->thr_high = thresholds[2]; a->thr_water = thresholds[3];
-    // numpy stores the class through a uint8 array: values wrap modulo 256 (the reference's pinned numpy 1.23.5 wraps;
-    // numpy 2 raises OverflowError instead).  Unsigned sums: 100 + INT32_MAX must wrap, not overflow.
-    a->low_class = (int)(uint8_t)(0u + (uint32_t)year_offset);
-    a->high_class = (int)(uint8_t)(100u + (uint32_t)year_offset);
+    land_resolve(a, forest_classes, n_forest_classes, thresholds, year_offset);      // (the uint8 wrap: dswx_land_mesh_rule.h)
     a->height = height; a->width = width;
     a->wc3 = worldcover_up3; a->cgls = copernicus; a->land = land;
     a->out_stride = land_tile_stride ? land_tile_stride : height * width;

@@ -22,12 +22,19 @@ Copernicus DEM as it ships): then it is laid onto the
 HLS grid grown by DEM_MARGIN_IN_PIXELS through a coordinate mesh computed on the host
 (proteus_amd.warp) and interpolated on the device (cubic, include/dswx_hip.h "resample": this
 project's own definition, gdal.Warp's is not pinned) -> GPU terrain-shadow kernel, SHAD and DEM
-layers.  `landcover_file` must be on the HLS grid and `worldcover_file` on the grid three times
-finer (-> GPU LAND aggregation), i.e. what the reference's own `_warp` calls would hand to its
-per-pixel code.  A DEM off the grid in a WGS 84 / UTM zone or in the product's own SRS is
+layers.  `landcover_file` on the HLS grid and `worldcover_file` on the grid three times
+finer (what the reference's own `_warp` calls would hand to its per-pixel code) go to the GPU
+LAND aggregation as before.  If either is NOT on its grid -- the maps as they ship, in EPSG:4326 at
+1/1008 and 1/12000 degree; also a map in a WGS 84 / UTM zone or in the product's SRS off the grid --
+each map is planned on its own (proteus_amd.landmesh.plan), only the two source windows are read,
+and one kernel reads them through their meshes, nearest pixel, and writes LAND (include/dswx_hip.h
+"land mesh": this project's own definition, gdal.Warp's choice of the nearest pixel is not pinned).
+A tap that falls off a map reads the file's nodata value (0 without one), with a WARNING.
+A DEM off the grid in a WGS 84 / UTM zone or in the product's own SRS is
 resampled the same way only with the keyword extension `resample_projected_dem=True`: without
 it such a file is refused as it always was (a DEM a few metres off the grid is more often a
-mistake than an intention).  Land cover that still needs warping, a DEM in any other SRS and
+mistake than an intention).  Land cover in any other SRS, rotated, of several bands or not uint8, or
+across the antimeridian, a DEM in any other SRS and
 `shoreline_shapefile` raise NotImplementedError.  Pre-gridded planes can
 also be handed over directly with the `landcover_mask=`, `shadow_layer=` and `ocean_mask=`
 keyword extensions (arrays or GeoTIFF paths).
@@ -38,6 +45,7 @@ import logging
 import os
 import sys
 import threading
+import time
 from collections import OrderedDict
 from datetime import datetime
 
@@ -1051,12 +1059,8 @@ def dem_resample_plan(dem_info, geotransform, geo_tags, length, width, projected
         if deviation <= 1.0:
             break
     # the source window: the extent of the nodes, widened by the cubic halo and the deviation, clipped to the file
-    pad = 3 + int(np.ceil(deviation / 256.0))
-    x, y = mesh[..., 0].astype(np.int64), mesh[..., 1].astype(np.int64)
-    x0, x1 = max(int(x.min() >> 8) - pad, 0), min(int(x.max() >> 8) + pad + 1, dem_info.width)
-    y0, y1 = max(int(y.min() >> 8) - pad, 0), min(int(y.max() >> 8) + pad + 1, dem_info.height)
-    window = (x0, y0, max(x1 - x0, 0), max(y1 - y0, 0)) if x1 > x0 and y1 > y0 else (0, 0, 0, 0)
-    moved = np.clip(np.stack([x - 256 * window[0], y - 256 * window[1]], axis=-1), -(1 << 31), (1 << 31) - 1).astype(np.int32)
+    from . import landmesh
+    window, moved = landmesh.source_window(mesh, deviation, dem_info.height, dem_info.width, pad=3)
     return window, moved, shift, deviation, dst_shape
 
 
@@ -1124,34 +1128,93 @@ def _worldcover_year(metadata, worldcover_file_description):
     return 2000
 
 
+def _map_outside(info):
+    """The byte of a tap that falls off a land-cover map: the file's nodata value if it has one and is 0 .. 255, else 0 -- what
+    gdal.Warp initialises a destination to."""
+    nd = info.nodata
+    return int(nd) if nd is not None and not np.isnan(nd) and 0 <= nd <= 255 and float(nd) == int(nd) else 0
+
+
+def _landcover_mask_through_meshes(cg_file, cg_dir, cg_on, wc_file, wc_dir, wc_on, worldcover_file_description, mask_type,
+                                   geotransform, geo_tags, length, width, forest_classes, device, engine):
+    """create_landcover_mask when a map is NOT on the product grid: each map planned on its own, the two source windows read on
+    the host and uploaded, one launch of dswx_land_mesh_device.  Returns LAND: a DevicePlane with an engine, else an ndarray."""
+    from . import landmesh
+    for name, d in (('landcover_file', cg_dir), ('worldcover_file', wc_dir)):
+        if d.spp != 1 or d.info.dtype != np.uint8:
+            raise NotImplementedError(f'{name} has {d.spp} band(s) of {d.info.dtype}: a land-cover map is one uint8 band')
+    plans = {}
+    for name, d, on, scale in (('WorldCover', wc_dir, wc_on, 3), ('CGLS', cg_dir, cg_on, 1)):
+        try:
+            window, mesh, shift, deviation = landmesh.plan(d.info, geotransform, geo_tags or {}, length, width, scale, on_grid=on)
+        except NotImplementedError as e:
+            raise NotImplementedError(f'{"worldcover_file" if scale == 3 else "landcover_file"} is neither on the product grid nor a '
+                                      f'map that is laid onto it on the device: {e}')
+        logger.info(f'    {name} map {"on" if on else "NOT on"} its grid: nearest pixel on the device, mesh shift {shift}, '
+                    f'deviation {deviation:.2f}/256 source pixel, source window {window}')
+        plans[name] = (window, mesh, shift)
+    logger.info(f'    CGLS Land Cover 100m forest classes: {forest_classes}')
+    year = _worldcover_year(wc_dir.info.metadata, worldcover_file_description)
+    t0 = time.perf_counter()
+    def read(path, window):           # (a map that misses the tile has an empty window: an empty raster, every tap `outside`)
+        if window[2] == 0:
+            return np.zeros((0, 0), dtype=np.uint8)
+        return np.ascontiguousarray(geotiff.read_geotiff(path, window=window)[0], dtype=np.uint8)
+    wc, cg = read(wc_file, plans['WorldCover'][0]), read(cg_file, plans['CGLS'][0])
+    logger.info(f'    source windows read on the host in {time.perf_counter() - t0:.3f} s')
+    spec = landmesh.Spec(plans['WorldCover'][2], plans['CGLS'][2], _map_outside(wc_dir.info), _map_outside(cg_dir.info),
+                         landcover_threshold_dict[mask_type.lower()], year - 2000, forest_classes)
+    if engine is not None:
+        planes = [engine.upload(a) if a.size else engine.plane(a.shape, np.uint8) for a in (wc, cg)]
+        try:
+            land, head = engine.landcover_mask_mesh(planes[0], planes[1], plans['WorldCover'][1], plans['CGLS'][1], (length, width), spec)
+        finally:
+            for p in planes:
+                p.release()
+    else:
+        land, head = get_context(device).land_mesh(wc, cg, plans['WorldCover'][1], plans['CGLS'][1], (length, width), spec)
+    for name, word, of in (('ESA WorldCover', 2, 9 * length * width), ('Copernicus CGLS', 4, length * width)):
+        if int(head[word]):
+            logger.warning(f'WARNING the {name} map does not cover the HLS tile: {int(head[word])} of {of} taps fall outside it '
+                           f'and read {spec.outside_wc if word == 2 else spec.outside_cg}')
+    return land
+
+
 def create_landcover_mask(copernicus_landcover_file, worldcover_file, worldcover_file_description,
                           output_file, scratch_dir, mask_type, geotransform, projection, length, width,
                           forest_mask_landcover_classes, dswx_metadata_dict=None,
                           output_files_list=None, temp_files_list=None, *, geo_tags=None, device=None, engine=None):
     """LAND layer from the Copernicus CGLS 100 m and ESA WorldCover 10 m maps (:906-1115) with the
-    3 x 3 aggregation and class hierarchy on the GPU (dswx_landcover_mask_host).  The two
-    reprojections of the reference (`_warp`, nearest, :970-992) are GDAL's: here both rasters must
-    already be on the product grid -- CGLS on the HLS grid, WorldCover on the grid three times
-    finer -- otherwise NotImplementedError.  Returns the uint8 mask (None if a file is missing)."""
+    3 x 3 aggregation and class hierarchy on the GPU.  Both rasters on the product grid -- CGLS on the
+    HLS grid, WorldCover on the grid three times finer --: dswx_landcover_mask_host.  Otherwise the two
+    reprojections of the reference (`_warp`, nearest, :970-992) run on the device too: each map is
+    planned on its own (landmesh.plan: a north-up raster of one uint8 band in EPSG:4326, in a WGS 84 /
+    UTM zone or in the product's SRS), only the two source windows are read on the host, and ONE
+    launch reads them through their meshes and writes LAND (dswx_land_mesh_device).  Anything else:
+    NotImplementedError, which says what is taken.  Returns the uint8 mask (None if a file is missing)."""
     logger.info('creating LAND layer combining Copernicus Landcover 100m and ESA WorldCover 10m maps')
     for f in (copernicus_landcover_file, worldcover_file):
         if not os.path.isfile(f):
             logger.error(f'ERROR file not found: {f}')
             return None
-    if engine is not None:
-        # resident: both maps inflated on host threads, untiled on the device, aggregated there; the LAND layer stays in HBM
-        # for the classifier and leaves as COG blocks (pipeline.TileEngine)
-        cg_dir, wc_dir = geotiff.open_geotiff(copernicus_landcover_file), geotiff.open_geotiff(worldcover_file)
-        cg_info, wc_info = cg_dir.info, wc_dir.info
-    else:
+    cg_dir, wc_dir = geotiff.open_geotiff(copernicus_landcover_file), geotiff.open_geotiff(worldcover_file)
+    cg_info, wc_info = cg_dir.info, wc_dir.info
+    cg_on = _grid_margin(cg_info, geotransform, length, width) == 0
+    wc_on = _grid_margin(wc_info, geotransform, length, width, scale=3) == 0
+    if not (cg_on and wc_on):
+        land = _landcover_mask_through_meshes(copernicus_landcover_file, cg_dir, cg_on, worldcover_file, wc_dir, wc_on,
+                                              worldcover_file_description, mask_type, geotransform, geo_tags, length, width,
+                                              forest_mask_landcover_classes, device, engine)
+        if output_file:
+            _save_array(land, output_file, dswx_metadata_dict, geo_tags,
+                        description=band_description_dict['LAND'], output_files_list=output_files_list,
+                        ctable=_get_landcover_mask_ctable(), no_data_value=UINT8_FILL_VALUE)
+        return land
+    # both maps on the product grid.  Resident (engine): both maps inflated on host threads, untiled on the device, aggregated
+    # there; the LAND layer stays in HBM for the classifier and leaves as COG blocks (pipeline.TileEngine)
+    if engine is None:
         cg, cg_info = geotiff.read_geotiff(copernicus_landcover_file)
         wc, wc_info = geotiff.read_geotiff(worldcover_file)
-    if _grid_margin(cg_info, geotransform, length, width) != 0 or \
-            _grid_margin(wc_info, geotransform, length, width, scale=3) != 0:
-        raise NotImplementedError(
-            'landcover_file / worldcover_file are not on the product grid (CGLS: HLS grid; WorldCover: '
-            '3x finer): reprojecting them needs GDAL, which stays on the host and is outside this '
-            'drop-in (SURVEY.md section 2)')
     logger.info(f'    CGLS Land Cover 100m forest classes: {forest_mask_landcover_classes}')
     year = _worldcover_year(wc_info.metadata, worldcover_file_description)
     if engine is not None:

@@ -207,6 +207,39 @@ class DevicePlane:
         return self._through_mesh('resample', mesh, dst_shape, shift, want, _capi._resample_planes, _capi.ResampleOut,
                                   lambda stride: _resample.Spec(self.dtype, method, shift, nodata, outside, mesh_tile_stride_nodes=stride))
 
+    def land_mesh(self, copernicus, mesh_wc, mesh_cg, shape, spec, want=('land', 'head')):
+        """This uint8 [wc_h, wc_w] plane as the WorldCover source window and `copernicus` (a DevicePlane uint8 [cg_h, cg_w]) as
+        the CGLS one, read through the host meshes mesh_wc (of the lattice 3 H x 3 W) and mesh_cg (of shape = (H, W)) by `spec`
+        (a landmesh.Spec) as they lie in HBM (dswx_land_mesh_device, ONE launch; proteus_amd.landmesh.land_tiles of the same
+        arrays gives the same arrays): a dict of DevicePlanes for the outputs named in `want` -- 'land' uint8 [H, W], 'head'
+        uint64 [1, 8] -- which stay on the device."""
+        from .warp import mesh_shape
+        H, W = (int(v) for v in shape)
+        if len(self.shape) != 2 or len(copernicus.shape) != 2 or self.dtype != np.uint8 or copernicus.dtype != np.uint8:
+            raise ValueError(f'the maps are uint8 [h, w] planes, not {self.dtype} {self.shape} and {copernicus.dtype} {copernicus.shape}')
+        if spec.land_tile_stride or spec.wc_tile_stride or spec.cg_tile_stride:
+            raise ValueError('one tile: the strides of the spec must be 0')
+        meshes = []
+        for name, mesh, dims, shift in (('mesh_wc', mesh_wc, (3 * H, 3 * W), spec.shift_wc), ('mesh_cg', mesh_cg, (H, W), spec.shift_cg)):
+            mesh = np.ascontiguousarray(mesh, dtype=np.int32)
+            if mesh.shape != mesh_shape(dims, shift) + (2,):
+                raise ValueError(f'{name} for {dims} at shift {shift} is {mesh_shape(dims, shift) + (2,)}, not {mesh.shape}')
+            meshes.append(mesh)
+        want = _capi._wanted(want, {'land': 0, 'head': 0})
+        made = {k: self.engine.plane(*{'land': ((H, W), np.uint8), 'head': ((1, _capi.LAND_MESH_HEAD_WORDS), np.uint64)}[k])
+                for k in ('land', 'head') if k in want}
+        tables = [self.engine.upload(m) for m in meshes]
+        try:
+            with self.engine.lock, stages.span('gpu: LAND through meshes'):
+                self.engine.ctx.land_mesh_device(self.ptr, self.shape, copernicus.ptr, copernicus.shape, spec, 1, H, W, tables[0].ptr,
+                                                 tables[1].ptr, made['land'].ptr if 'land' in made else None,
+                                                 made['head'].ptr if 'head' in made else None)
+                self.engine.ctx.synchronize()
+        finally:
+            for t in tables:
+                t.release()
+        return made
+
     def grid(self, spec, want=('count', 'share', 'coverage', 'major')):
         """The rasters of a [n, H, W] (or one [H, W]) uint8 plane aggregated onto cells as they lie in HBM (dswx_grid_device;
         proteus_amd.grid.grid_tiles of the same array gives the same planes): a dict of [n, GH, GW] DevicePlanes for the
@@ -426,13 +459,19 @@ class TileEngine:
         n = self._round(nbytes)
         with self._pool_lock:
             spare = self._free.get(n)
-            if spare:
+            while spare:
                 self._free_bytes -= n
-                return spare.pop()
+                buf = spare.pop()
+                # a plane that dies inside a reference cycle (the frames of a refused run, held by its traceback) is finalised
+                # together with its buffer, in either order: the buffer may have been freed although it was given back
+                if buf.ptr:
+                    return buf
         with self.lock:
             return self.ctx.malloc(n)
 
     def _give(self, buf):
+        if not buf.ptr:                      # freed already by its own finalizer (see _take)
+            return
         with self._pool_lock:
             if self.ctx.handle and self._free_bytes + buf.nbytes <= self.POOL_CAP:
                 self._free.setdefault(buf.nbytes, []).append(buf)
@@ -633,6 +672,17 @@ class TileEngine:
                                            thresholds=thresholds, year_offset=year_offset)
             self.ctx.synchronize()
         return out
+
+    def landcover_mask_mesh(self, worldcover, copernicus, mesh_wc, mesh_cg, shape, spec):
+        """Source windows of the two maps (DevicePlanes, u8, NOT on the product grid) read through their meshes -> (LAND
+        DevicePlane [H, W], head uint64 [8] on the host): create_landcover_mask's two warps and its per-pixel part in one
+        launch (DevicePlane.land_mesh)."""
+        made = worldcover.land_mesh(copernicus, mesh_wc, mesh_cg, shape, spec)
+        try:
+            head = made['head'].numpy().reshape(-1)
+        finally:
+            made['head'].release()
+        return made['land'], head
 
     # ---- writer side ----------------------------------------------------------------------------------------
     WEIGHTS_CAP = 64            # (n_in, n_out) pairs kept: a worker sees one tile size, i.e. about ten pairs
