@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""`dswx_burn.py product.tif --polygons FILE.geojson [--burn 1] [--background 0] [--buffer-m M] [--device D] --out FILE.tif`
+"""`dswx_burn.py product.tif --polygons FILE.geojson [--burn 1] [--background 0] [--buffer-m M | --buffer-vector-m M] [--device D] --out FILE.tif`
 
 Polygons burnt onto the grid of a DSWx-HLS product on the GPU (include/dswx_hip.h "burn"): the opposite direction of
 dswx_outline.py, which writes the files this tool reads, so the two round-trip.  FILE.geojson holds Polygon / MultiPolygon
@@ -9,7 +9,9 @@ a plane of the product's size that starts as --background, 32 polygons per call 
 its bit, IN PLACE: a pixel whose CENTRE lies inside a polygon (even-odd within one polygon) becomes --burn, and polygons that
 overlap union.  16 bytes per vertex cross PCIe, not a plane.  With --buffer-m every pixel within M metres of a burnt pixel is
 set to --burn too, through the distance entry's `within` (include/dswx_hip.h "distance"): that buffers the RASTER -- distances
-between pixel centres, M rounded down to whole pixels -- not the vector as the reference's Buffer(margin) does.  FILE.tif is
+between pixel centres, M rounded down to whole pixels -- not the vector as the reference's Buffer(margin) does.  With
+--buffer-vector-m every pixel whose CENTRE lies within M metres of an edge of a polygon is set to --burn too, through the reach
+entry (include/dswx_hip.h "reach"): that buffers the VECTOR, exactly, M rounded to 1/256 pixel.  FILE.tif is
 written as a Byte COG with the product's georeferencing, usable as --ocean-mask (with --burn 0 --background 1: 0 = ocean).
 One line of JSON on standard output says how many polygons, rings and vertices there were and how many pixels were burnt.
 """
@@ -86,6 +88,8 @@ def main(argv=None):
     ap.add_argument('--burn', type=int, default=1, help='byte of a pixel inside a polygon (default 1)')
     ap.add_argument('--background', type=int, default=0, help='byte of every other pixel (default 0)')
     ap.add_argument('--buffer-m', type=float, default=None, metavar='M', help='also burn every pixel within M metres of a burnt pixel (buffers the RASTER)')
+    ap.add_argument('--buffer-vector-m', type=float, default=None, metavar='M',
+                    help='also burn every pixel whose centre lies within M metres of a polygon edge (buffers the VECTOR, exactly)')
     ap.add_argument('--device', type=int, default=None, metavar='D', help='GPU to run on (default $DSWX_DEVICE or 0)')
     args = ap.parse_args(argv)
     for f in (args.input_file, args.polygons):
@@ -98,7 +102,11 @@ def main(argv=None):
     if args.buffer_m is not None and not args.buffer_m > 0:
         print(f'ERROR --buffer-m {args.buffer_m}: above 0')
         return 1
+    if args.buffer_vector_m is not None and (args.buffer_m is not None or not args.buffer_vector_m >= 0):
+        print(f'ERROR --buffer-vector-m {args.buffer_vector_m}: 0 or above, and not together with --buffer-m')
+        return 1
     from proteus_amd import dswx_hls, geotiff, pipeline
+    from proteus_amd import reach as RC
     from proteus_amd.distance import Spec as DistanceSpec
     try:
         with open(args.polygons) as f:
@@ -117,6 +125,13 @@ def main(argv=None):
     plane = engine.constant_plane((H, W), args.background)
     spec = BN.Spec(burn=args.burn, background=args.background)
     toggles = rings = vertices = 0
+    reach_spec = None
+    if args.buffer_vector_m is not None:
+        if abs(gt[5]) != abs(gt[1]) or not 256.0 * args.buffer_vector_m / abs(gt[1]) <= RC.MAX_RADIUS:
+            print(f'ERROR --buffer-vector-m {args.buffer_vector_m}: needs square pixels (here {abs(gt[1])} x {abs(gt[5])} m) and at most '
+                  f'{RC.MAX_RADIUS // 256} pixels')
+            return 1
+        reach_spec = RC.Spec(int(round(256.0 * args.buffer_vector_m / abs(gt[1]))), burn=args.burn, background=args.background)
     try:
         for at in range(0, len(polys), POLYGONS_PER_CALL):
             px, words = rings_of(polys[at:at + POLYGONS_PER_CALL], gt)
@@ -126,11 +141,18 @@ def main(argv=None):
             vertices += sum(len(r) for r in px)
             for p in res.values():
                 p.release()
+        if reach_spec is not None:                               # every ring at once: no bit is needed to reach
+            res = plane.reach([to_pixels(r, gt) for p in polys for r in p], reach_spec, want=('head',))
+            reached = int(res['head'].numpy()[0, 6])
+            for p in res.values():
+                p.release()
     except ValueError as e:
         print(f'ERROR {e}')
         return 1
     said = {'input_file': os.path.basename(args.input_file), 'polygons': len(polys), 'rings': rings, 'vertices': vertices,
             'toggles': toggles, 'height': H, 'width': W, 'burn': args.burn, 'background': args.background}
+    if reach_spec is not None:
+        said['buffer_vector_256ths_of_a_pixel'], said['reached_pixels'] = reach_spec.radius, reached
     if args.buffer_m is not None:
         px_m = abs(gt[1])
         if abs(gt[5]) != px_m:
@@ -150,6 +172,8 @@ def main(argv=None):
     md = {'BURN_INPUT_FILE': os.path.basename(args.input_file), 'BURN_POLYGONS_FILE': os.path.basename(args.polygons),
           'BURN_VALUE': str(args.burn), 'BURN_BACKGROUND': str(args.background),
           'BURN_BUFFER_M': str(args.buffer_m) if args.buffer_m is not None else 'none (the raster, not the vector, is buffered)'}
+    if reach_spec is not None:
+        md['BURN_BUFFER_M'], md['BURN_BUFFER_VECTOR_M'] = 'none', str(args.buffer_vector_m)
     written = []
     dswx_hls._save_array(plane, args.out, md, info.geo_tags, description='Polygons burnt onto the grid of the product',
                          output_files_list=written)

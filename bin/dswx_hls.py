@@ -36,7 +36,7 @@ def main(argv=None):
               'worldcover_file', 'worldcover_file_description', 'shoreline_shapefile',
               'shoreline_shapefile_description', 'flag_offset_and_scale_inputs', 'scratch_dir',
               'product_id', 'product_version', 'flag_debug', 'landcover_mask', 'shadow_layer',
-              'ocean_mask', 'device'):
+              'ocean_mask', 'device', 'rasterise_shoreline'):
         kwargs[k] = getattr(args, k)
     ok = generate_dswx_layers(args.input_list, args.output_file,
                               hls_thresholds=consts.hls_thresholds, **kwargs)

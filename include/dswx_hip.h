@@ -1173,8 +1173,9 @@ int dswx_outline_host(const uint32_t* ids, const dswx_outline_spec_t* spec, int6
  * become pixels, without a plane crossing PCIe -- a coastline, an area of interest or an edited lake polygon becomes a plane
  * on the device, or is burnt straight into the OCEAN plane of a resident batch in front of dswx_batch_classify.  What the
  * reference does with gdal.RasterizeLayer(burn_values=[1]) in _create_ocean_mask (dswx_hls.py:3464-3572).  A C caller tests
- * for the entries with DSWX_HAS_BURN.  STILL REFUSED: reading .shp files, reprojecting from the SRS of a shapefile, and the
- * metric Buffer(margin_m) of the VECTOR (the distance entry's `within` buffers the RASTER afterwards).
+ * for the entries with DSWX_HAS_BURN.  The metric Buffer(margin_m) of the VECTOR is the "reach" block below (the distance
+ * entry's `within` buffers the RASTER afterwards).  STILL REFUSED by this library: reading .shp files and reprojecting from
+ * the SRS of a shapefile -- host work, which proteus_amd/shoreline.py does for WGS 84 geographic and WGS 84 / UTM.
  * UNPINNED: GDAL is not part of this project's environment, so GDAL's handling of a pixel centre that lies exactly on an edge
  * is not pinned by any test.  The definition below is this project's own; it agrees with GDAL's documented default (a pixel
  * is burnt when its CENTRE is inside) wherever no centre lies exactly on an edge.
@@ -1266,6 +1267,75 @@ int dswx_batch_burn(dswx_batch_t* batch, int32_t plane, const dswx_burn_vertex_t
  * buffer may sit at any address. */
 int dswx_burn_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles,
                    int64_t height, int64_t width, const uint8_t* src, const dswx_burn_out_t* out_host);
+
+/* ---- reach: every pixel whose centre lies within a radius of a polygon edge -- the exact buffer (additive to ABI v7) --------
+ * The burn entries give the inside of polygons.  These give the pixels NEAR their edges, measured from pixel centres to the
+ * vector itself: burn, then reach onto the same mask (`src` == `mask`), is the polygon grown by the radius -- what the
+ * reference does with Buffer(margin_m) in front of gdal.RasterizeLayer in _create_ocean_mask (dswx_hls.py:3464-3572).  A C
+ * caller tests for the entries with DSWX_HAS_REACH.
+ * UNPINNED: GDAL and GEOS are not part of this project's environment.  OGR's Buffer replaces the circle at a convex vertex by
+ * chords (30 segments per quadrant by default) that lie inside it by at most r (1 - cos 1.5 deg) = 3.4e-4 r; an exact buffer
+ * differs from it only in centres inside that sliver.  No test pins the two to each other.
+ * THE DEFINITION.  Records, `tile_first`, the count of a tile, legality (|v| <= 2^30) and MALFORMED are those of the burn block
+ * above, to the letter -- `next` is compared with the count before the record it names is read -- and so are the coordinates:
+ * int32 in 1/256 pixel, the centre of pixel (c, r) at P = (256 c + 128, 256 r + 128).  `word` is ignored.  NOTHING IS DROPPED:
+ * a horizontal edge takes part, and an edge whose two endpoints coincide is a point and takes part.
+ *   RADIUS     `radius`: uint32 in 1/256 pixel, 0 <= radius <= DSWX_REACH_MAX_RADIUS = 2^20 (4096 pixels).
+ *   REACHED    pixel (c, r) is REACHED by the well-formed edge A -> B iff the squared Euclidean distance from P to the closed
+ *              segment is <= radius^2, in exact integers: with d = B - A, u = P - A, D = d.d, t = u.d and R = radius,
+ *                  D == 0 or t <= 0:   u.u <= R^2
+ *                  t >= D:             |P - B|^2 <= R^2
+ *                  otherwise:          (u x d)^2 <= R^2 D
+ *              stated in unbounded integers: at the extreme coordinates u x d and t pass 2^63 and R^2 D reaches 2^103.
+ *   acc        uint32 [n_tiles][height * width], dense.  REQUIRED: it is the working array.  acc[r][c] is the number of
+ *              well-formed edges of the tile that reach (c, r), modulo 2^32;
+ *   mask       uint8 [n_tiles][mask_tile_stride] (0 = height * width): mask[p] = acc[p] != 0 ? burn : (src ? src[p] :
+ *              background), strides, `src` and `src` == `mask` as for the burn entries: reach ORed onto a burnt mask;
+ *   head       uint64 [n_tiles][DSWX_REACH_HEAD_WORDS]: word 0 the records of the tile; 1 the malformed ones; 2 the edges that
+ *              reach at least one pixel of the tile; 3 the (edge, row) intervals applied -- the capsule of an edge is convex, so
+ *              the pixels of a row that it reaches are one interval of columns; 4 the applied intervals cut at column 0 (the
+ *              edge also reaches the centre of column -1 of that row); 5 those cut at column width - 1 (it also reaches the
+ *              centre of column `width`); 6 the pixels with acc != 0; 7 zero.  NULL = not wanted.
+ * height * width <= 2^30.  n_tiles == 0 writes nothing.  All of it is integer arithmetic (floating point only proposes where
+ * an interval ends; the exact predicate decides): deterministic and independent of the launch geometry and of the order in
+ * which atomics arrive. */
+#define DSWX_HAS_REACH 1
+#define DSWX_REACH_HEAD_WORDS 8
+#define DSWX_REACH_MAX_RADIUS (1 << 20)
+typedef struct dswx_reach_spec {
+    int32_t burn;                      /* 0 .. 255: the byte of a pixel with acc != 0 in `mask` */
+    int32_t background;                /* 0 .. 255: the byte of every other pixel when there is no `src` */
+    int64_t mask_tile_stride;          /* elements between the tiles of `mask`; 0 = height * width */
+    int64_t src_tile_stride;           /* elements between the tiles of `src`; 0 = height * width */
+    uint32_t radius;                   /* 1/256 pixel, 0 .. DSWX_REACH_MAX_RADIUS */
+    uint32_t reserved;                 /* must be 0 */
+} dswx_reach_spec_t;                   /* 32 bytes */
+typedef dswx_burn_out_t dswx_reach_out_t;      /* acc (REQUIRED), mask, head: as for the burn entries */
+/* Records and table in DEVICE memory -> the wanted outputs of *out_device (device memory).  Asynchronous on `stream` (NULL =
+ * the context's stream): one hipMemsetAsync each of `acc` and `head` and two kernel launches -- every (edge, row) adds +1 at
+ * the first reached column and -1 behind the last one with two atomic adds on `acc` (the rows of an edge are shared out over
+ * the lanes of its wave); then a prefix sum along every row of `acc` in place, which also writes `mask` and counts the pixels.
+ * No synchronisation, no scratch of the context, no allocation, no working memory and nothing the caller has to zero in
+ * front: a second call on the same outputs gives the same bytes.  No workgroup ever waits for another.  `tile_first` is read ON
+ * THE DEVICE ONLY, as for dswx_burn_device.  The refusals and alignments of dswx_burn_device, and a radius above
+ * DSWX_REACH_MAX_RADIUS or a `reserved` that is not 0: DSWX_ERR_ARG.  (The arguments are checked before the context is, and a
+ * refused call writes nothing.) */
+int dswx_reach_device(dswx_ctx_t* ctx, const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_reach_spec_t* spec,
+                      int64_t n_tiles, int64_t height, int64_t width, const uint8_t* src, const dswx_reach_out_t* out_device,
+                      void* stream);
+/* The twin of dswx_batch_burn: plane `plane` (a uint8 DSWX_PLANE_*; DSWX_PLANE_OCEAN is the natural target) of a resident batch
+ * is BOTH `mask` and `src`, at the batch's tile stride, for tiles tile0 .. tile0 + n_tiles - 1: the pixels within the radius of
+ * an edge become `burn` in place, every other pixel stays.  acc_device (required) and head_device (NULL = not wanted) are the
+ * caller's device memory with tile 0 = tile0.  Asynchronous like dswx_reach_device.  The two strides of `spec` must be 0.  The
+ * refusals of dswx_batch_burn. */
+int dswx_batch_reach(dswx_batch_t* batch, int32_t plane, const dswx_burn_vertex_t* verts_device, const int64_t* tile_first_device,
+                     const dswx_reach_spec_t* spec, uint32_t* acc_device, uint64_t* head_device, int64_t tile0, int64_t n_tiles,
+                     void* stream);
+/* The same definition on HOST buffers in plain scalar C++: needs no device and no context.  The other half of a comparison,
+ * not a fallback of the two entries above.  The refusals of dswx_reach_device, except that every buffer may sit at any
+ * address. */
+int dswx_reach_host(const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_reach_spec_t* spec, int64_t n_tiles,
+                    int64_t height, int64_t width, const uint8_t* src, const dswx_reach_out_t* out_host);
 
 /* ---- mosaic: tiles placed on one canvas and composited per canvas pixel -- a stack with placements (additive to ABI v7) ---
  * Every entry above treats a tile on its own, and a stack requires every tile to cover the same pixels.  Neighbouring MGRS

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     'dswx_distance_device', 'dswx_batch_distance', 'dswx_distance_host',
     'dswx_outline_work_bytes', 'dswx_outline_device', 'dswx_outline_host',
     'dswx_burn_device', 'dswx_batch_burn', 'dswx_burn_host',
+    'dswx_reach_device', 'dswx_batch_reach', 'dswx_reach_host',
     'dswx_mosaic_device', 'dswx_batch_mosaic', 'dswx_mosaic_host',
     'dswx_warp_device', 'dswx_batch_warp', 'dswx_warp_host',
     'dswx_resample_device', 'dswx_resample_host',
@@ -83,6 +84,10 @@ BURN_HEAD_WORDS, BURN_MAX_COORD = 8, 1 << 30
 # csrc/dswx_burn_rule.h: the rows of an edge that its own thread finishes (a longer edge is shared out over the wave) and the
 # pixels of a row that a wave of the scan launch takes per step (tests build shapes around the seams)
 BURN_THREAD_ROWS, BURN_SCAN_STEP = 4, 256
+HAS_REACH = 1                     # DSWX_HAS_REACH: additive to ABI v7
+REACH_HEAD_WORDS, REACH_MAX_RADIUS = 8, 1 << 20
+# csrc/dswx_reach_rule.h: as for the burn (tests build shapes around the seams)
+REACH_THREAD_ROWS, REACH_SCAN_STEP = 4, 256
 HAS_MOSAIC = 1                    # DSWX_HAS_MOSAIC: additive to ABI v7
 # csrc/dswx_mosaic.hip: the rows and the columns of the canvas rectangle of one workgroup, the tiles of the surviving-tile list
 # in LDS, the placements tested per step and the loads in flight per thread (tests build shapes around the seams)
@@ -410,6 +415,15 @@ class BurnSpec(ctypes.Structure):
         return cls(spec.burn, spec.background, spec.mask_tile_stride, spec.src_tile_stride)
 
 
+class ReachSpec(ctypes.Structure):
+    """dswx_reach_spec_t; proteus_amd.reach.Spec is the Python form."""
+    _fields_ = BurnSpec._fields_ + [('radius', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+    @classmethod
+    def of(cls, spec):
+        return cls(spec.burn, spec.background, spec.mask_tile_stride, spec.src_tile_stride, spec.radius, spec.reserved)
+
+
 class BurnOut(ctypes.Structure):
     """dswx_burn_out_t: addresses, 0 / None = not wanted."""
     _fields_ = [('acc', ctypes.c_void_p), ('mask', ctypes.c_void_p), ('head', ctypes.c_void_p)]
@@ -423,7 +437,8 @@ class BurnOut(ctypes.Structure):
 ANALYTIC_STRUCTS = {'dswx_label_spec_t': LabelSpec, 'dswx_label_out_t': LabelOut, 'dswx_body_spec_t': BodySpec,
                     'dswx_body_out_t': BodyOut, 'dswx_distance_spec_t': DistanceSpec, 'dswx_distance_out_t': DistanceOut,
                     'dswx_outline_spec_t': OutlineSpec, 'dswx_outline_out_t': OutlineOut,
-                    'dswx_burn_spec_t': BurnSpec, 'dswx_burn_out_t': BurnOut}
+                    'dswx_burn_spec_t': BurnSpec, 'dswx_burn_out_t': BurnOut,
+                    'dswx_reach_spec_t': ReachSpec}
 
 COG_MAX_LEVELS = 8
 
@@ -626,6 +641,9 @@ def load_library(path=None):
         'dswx_burn_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
         'dswx_batch_burn': (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp, vp, vp, i64, i64, vp]),
         'dswx_burn_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
+        'dswx_reach_device': (ctypes.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]),
+        'dswx_batch_reach': (ctypes.c_int, [vp, ctypes.c_int32, vp, vp, vp, vp, vp, i64, i64, vp]),
+        'dswx_reach_host': (ctypes.c_int, [vp, vp, vp, i64, i64, i64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         if alt and not hasattr(lib, name):
@@ -1388,6 +1406,15 @@ class Context:
                                          int(n_tiles), int(height), int(width), ctypes.c_void_p(src_ptr) if src_ptr else None,
                                          ctypes.byref(out), _stream_arg(stream)))
 
+    def reach_device(self, verts_ptr, tile_first_ptr, spec, n_tiles, height, width, src_ptr, out, stream=None):
+        """dswx_reach_device: as burn_device, for the pixels whose centre lies within spec.radius of an edge of the records
+        (`spec` a reach.Spec; include/dswx_hip.h "reach", proteus_amd/reach.py states the definition in numpy); `src_ptr` may be
+        out.mask: the reach ORed onto a burnt mask.  Two memsets and two launches, asynchronous."""
+        _check(self.lib.dswx_reach_device(self.handle, ctypes.c_void_p(verts_ptr) if verts_ptr else None,
+                                          ctypes.c_void_p(tile_first_ptr) if tile_first_ptr else None, ctypes.byref(ReachSpec.of(spec)),
+                                          int(n_tiles), int(height), int(width), ctypes.c_void_p(src_ptr) if src_ptr else None,
+                                          ctypes.byref(out), _stream_arg(stream)))
+
     def burn(self, verts, tile_first, height, width, spec, src=None, want=('acc', 'mask', 'head'), stream=None):
         """Rings burnt onto new device planes: uploads the host records `verts` (burn.VERTEX_DTYPE) and the table `tile_first`
         (int64 [n_tiles + 1]), allocates the wanted outputs and 'acc' always, queues dswx_burn_device on `stream` and waits
@@ -1830,6 +1857,16 @@ def burn_host(verts, tile_first, height, width, spec, src=None, want=('acc', 'ma
     statement.  'mask' is uint8 [n_tiles, H, W], or [n_tiles, spec.mask_tile_stride] with a stride; `mask` names an array of
     that size to write into instead of a new one (the bytes between the rasters are left as they are), and `src` (uint8, of
     the size the spec's src stride implies) may be that very array: burnt in place."""
+    return _rings_host('dswx_burn_host', BurnSpec, verts, tile_first, height, width, spec, src, want, mask)
+
+
+def reach_host(verts, tile_first, height, width, spec, src=None, want=('acc', 'mask', 'head'), mask=None):
+    """dswx_reach_host (no device needed): the outputs of proteus_amd.reach.reach_tiles, with the arguments of burn_host and
+    `spec` a reach.Spec."""
+    return _rings_host('dswx_reach_host', ReachSpec, verts, tile_first, height, width, spec, src, want, mask)
+
+
+def _rings_host(entry, spec_struct, verts, tile_first, height, width, spec, src, want, mask):
     verts, tile_first, n = _burn_input(verts, tile_first)
     want = _burn_wanted(want)
     res = {k: np.zeros(_burn_shape(k, n, height, width, spec), dtype=BURN_DTYPES[k]) for k in want if not (k == 'mask' and mask is not None)}
@@ -1845,8 +1882,8 @@ def burn_host(verts, tile_first, height, width, spec, src=None, want=('acc', 'ma
             raise ValueError(f'src has {src.size} bytes, not {n} tiles of {spec.src_tile_stride or height * width}')
     dummy = np.zeros(1, dtype=verts.dtype)
     out = BurnOut.of(**{k: a.ctypes.data for k, a in res.items()})
-    _check(load_library().dswx_burn_host(_host_ptr(verts if verts.size else dummy), _host_ptr(tile_first), ctypes.byref(BurnSpec.of(spec)),
-                                         n, int(height), int(width), _host_ptr(src) if src is not None else None, ctypes.byref(out)))
+    _check(getattr(load_library(), entry)(_host_ptr(verts if verts.size else dummy), _host_ptr(tile_first), ctypes.byref(spec_struct.of(spec)),
+                                          n, int(height), int(width), _host_ptr(src) if src is not None else None, ctypes.byref(out)))
     return res
 
 
@@ -2238,6 +2275,16 @@ class DeviceBatch:
         DeviceBuffers / device addresses (asynchronous).  Returns {output: DeviceBuffer}: 'acc' uint32 [n_tiles][H*W] always
         (the working array), 'head' uint64 [n_tiles][8] when wanted -- device planes owned by the caller.
         proteus_amd.burn.burn_tiles with src = the downloaded plane gives the same plane and the same outputs."""
+        return self._rings('dswx_batch_burn', BurnSpec, name, verts, tile_first, spec, tile0, n_tiles, want, stream)
+
+    def reach(self, name, verts, tile_first, spec, tile0=0, n_tiles=None, want=('acc', 'head'), stream=None):
+        """dswx_batch_reach: the pixels of the uint8 plane `name` whose centre lies within spec.radius of an edge of the records
+        become spec.burn in place (`spec` a reach.Spec with both strides 0); everything else as for burn().  burn() then
+        reach() on 'ocean' is the buffered polygon.  proteus_amd.reach.reach_tiles with src = the downloaded plane gives the
+        same plane and the same outputs."""
+        return self._rings('dswx_batch_reach', ReachSpec, name, verts, tile_first, spec, tile0, n_tiles, want, stream)
+
+    def _rings(self, entry, spec_struct, name, verts, tile_first, spec, tile0, n_tiles, want, stream):
         plane = _plane_index(name)
         n_tiles, nt = self._tiles(tile0, n_tiles)
         want = _burn_wanted(tuple(want) + ('acc',))
@@ -2254,8 +2301,8 @@ class DeviceBatch:
                         temps[0].upload(verts)
                     temps[1].upload(tile_first)
                     verts, tile_first = temps
-                _check(self.ctx.lib.dswx_batch_burn(self.handle, plane, ctypes.c_void_p(getattr(verts, 'ptr', verts)),
-                                                    ctypes.c_void_p(getattr(tile_first, 'ptr', tile_first)), ctypes.byref(BurnSpec.of(spec)),
+                _check(getattr(self.ctx.lib, entry)(self.handle, plane, ctypes.c_void_p(getattr(verts, 'ptr', verts)),
+                                                    ctypes.c_void_p(getattr(tile_first, 'ptr', tile_first)), ctypes.byref(spec_struct.of(spec)),
                                                     ctypes.c_void_p(res['acc'].ptr), ctypes.c_void_p(res['head'].ptr) if 'head' in res else None,
                                                     int(tile0), n_tiles, _stream_arg(stream)))
                 if temps:

@@ -46,7 +46,8 @@ def _one_tile(D, device, path, skip_existing):
                   'dem_file', 'dem_file_description', 'landcover_file',
                   'landcover_file_description', 'worldcover_file', 'worldcover_file_description',
                   'shoreline_shapefile', 'shoreline_shapefile_description',
-                  'flag_offset_and_scale_inputs', 'landcover_mask', 'shadow_layer', 'ocean_mask'):
+                  'flag_offset_and_scale_inputs', 'landcover_mask', 'shadow_layer', 'ocean_mask',
+                  'rasterise_shoreline'):
             kw[k] = getattr(args, k)
         wanted = [kw[k] for k in kw if k.startswith('output_') and kw[k]] + \
             ([args.output_file] if args.output_file else [])

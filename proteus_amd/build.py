@@ -28,12 +28,13 @@ SOURCES = [os.path.join(CSRC, n) for n in ('dswx_hip.hip', 'dswx_classify_lut.hi
                                            'dswx_checksum.hip', 'dswx_compare.hip', 'dswx_histogram.hip', 'dswx_crosstab.hip',
                                            'dswx_stack.hip', 'dswx_grid.hip', 'dswx_label.hip', 'dswx_body_table.hip',
                                            'dswx_distance.hip', 'dswx_outline.hip', 'dswx_burn.hip', 'dswx_mosaic.hip', 'dswx_warp.hip',
-                                           'dswx_resample.hip', 'dswx_land_mesh.hip')]
+                                           'dswx_resample.hip', 'dswx_land_mesh.hip', 'dswx_reach.hip')]
 HEADERS = [os.path.join(CSRC, n) for n in ('dswx_device.h', 'dswx_host.h', 'dswx_tables.h', 'dswx_vmm.h',
                                            'dswx_hist_bin.h', 'dswx_stack_rule.h', 'dswx_stack_core.h', 'dswx_grid_rule.h',
                                            'dswx_label_rule.h', 'dswx_body_rule.h', 'dswx_distance_rule.h',
                                            'dswx_outline_rule.h', 'dswx_burn_rule.h', 'dswx_batch_select.h',
-                                           'dswx_mesh_rule.h', 'dswx_resample_rule.h', 'dswx_land_mesh_rule.h')]
+                                           'dswx_mesh_rule.h', 'dswx_resample_rule.h', 'dswx_land_mesh_rule.h',
+                                           'dswx_reach_rule.h', 'dswx_ring_scan.h')]
 LAB_SOURCES = [os.path.join(LAB, n) for n in ('dswx_lab.hip', 'dswx_probes.hip')]
 LAB_HEADERS = [os.path.join(LAB, 'dswx_lab.h')]
 INCLUDE = os.path.join(ROOT, 'include')

@@ -542,6 +542,25 @@ int dswx_batch_burn(dswx_batch_t* b, int32_t plane, const dswx_burn_vertex_t* ve
                             dswx_stream_of(ctx, stream));
 }
 
+// The pixels within a radius of polygon edges set IN one uint8 plane of a resident batch (dswx_reach.hip): the twin of
+// dswx_batch_burn above, with the same selection, the same strides and nothing allocated, copied or waited for.
+int dswx_batch_reach(dswx_batch_t* b, int32_t plane, const dswx_burn_vertex_t* verts, const int64_t* tile_first, const dswx_reach_spec_t* spec,
+                     uint32_t* acc, uint64_t* head, int64_t tile0, int64_t n_tiles, void* stream) {
+    dswx_batch_view v;
+    const uint8_t* base;
+    if (int rc = select_u8(b, plane, 0, "the counters are not reached into", "edges reach into a uint8 plane", tile0, &n_tiles, &v, &base)) return rc;
+    if (spec && (spec->mask_tile_stride || spec->src_tile_stride))
+        return dswx_fail(DSWX_ERR_ARG, "mask_tile_stride %lld and src_tile_stride %lld must be 0: the plane has the stride of the batch",
+                         (long long)spec->mask_tile_stride, (long long)spec->src_tile_stride);
+    const dswx_reach_out_t out = {acc, const_cast<uint8_t*>(base), head};
+    int64_t mask_stride, src_stride;
+    if (int rc = dswx_reach_check(verts, tile_first, spec, n_tiles, v.height, v.width, base, &out, &mask_stride, &src_stride, true)) return rc;
+    dswx_ctx* ctx = b->ctx;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return dswx_reach_launch(ctx, verts, tile_first, spec, n_tiles, v.height, v.width, base, v.tile_stride, v.tile_stride, &out,
+                             dswx_stream_of(ctx, stream));
+}
+
 // The tiles of ONE uint8 plane of a resident batch placed on a canvas and composited per canvas pixel (dswx_mosaic.hip), one
 // launch, asynchronous: the table and the outputs are the caller's device memory, so nothing is allocated, copied or waited
 // for here.  place[0] belongs to tile0, and last_index counts from tile0.

@@ -31,6 +31,7 @@
 
 #include "dswx_host.h"
 #include "dswx_burn_rule.h"
+#include "dswx_ring_scan.h"
 
 namespace {
 
@@ -43,27 +44,12 @@ constexpr int64_t BURN_MAX_PIXELS = 1LL << 30;
 constexpr unsigned BURN_TOGGLE_BLOCKS = 4096;            // the toggle launch: about this many workgroups over all tiles
 constexpr unsigned BURN_SCAN_BLOCKS = 4096;              // the scan launch: at most this many workgroups
 static_assert(DSWX_BURN_SCAN_STEP == 64 * 4, "a wave's step: 64 lanes of four pixels");
+static_assert(BURN_BLOCK == RING_BLOCK && DSWX_BURN_HEAD_WORDS == RING_HEAD_WORDS && BURN_HEAD_INSIDE == RING_HEAD_PIXELS, "dswx_ring_scan.h");
 static_assert(sizeof(dswx_burn_vertex_t) == 16 && sizeof(dswx_burn_spec_t) == 24, "the records and the spec of the header");
 
-struct BurnArgs {
-    const burn_u32x4* verts;
-    const long long* tile_first;
-    unsigned* acc;
-    unsigned char* mask;                                 // nullptr: not wanted
-    const unsigned char* src;                            // nullptr: the background
-    unsigned long long* head;                            // nullptr: not wanted
-    long long n_tiles, height, width;
-    unsigned long long n_elems;                          // height * width <= 2^30
-    unsigned long long mask_stride, src_stride;
-    unsigned burn, background;
-    unsigned long long total_rows, rows_per_block;       // the scan launch
-};
+typedef RingArgs BurnArgs;                               // (dswx_ring_scan.h: the fields of both launches)
 
-__device__ __forceinline__ unsigned burn_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
+__device__ __forceinline__ unsigned burn_wave_sum(unsigned v) { return ring_wave_sum(v); }
 
 // One crossing of row r: the toggle, and what the head counts of it.
 struct BurnCounts {
@@ -167,87 +153,8 @@ __global__ __launch_bounds__(BURN_BLOCK) void dswx_burn_toggle_k(const BurnArgs 
 static_assert(BURN_HEAD_MALFORMED == 1 && BURN_HEAD_EDGES == 2 && BURN_HEAD_TOGGLES == 3 && BURN_HEAD_DROPPED == 4 && BURN_HEAD_CLAMPED == 5,
               "the order of `sums` above");
 
-// ---- launch 2: the XOR prefix along every row, the mask, the pixels inside ---------------------------------------------------
-__device__ __forceinline__ void burn_flush_inside(const BurnArgs& a, long long t, unsigned* inside, unsigned lane) {
-    const unsigned sum = burn_wave_sum(*inside);
-    *inside = 0u;
-    if (a.head && sum && lane == 0u) atomicAdd(a.head + (unsigned long long)t * DSWX_BURN_HEAD_WORDS + BURN_HEAD_INSIDE, (unsigned long long)sum);
-}
-
-__global__ __launch_bounds__(BURN_BLOCK) void dswx_burn_scan_k(const BurnArgs a) {
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const unsigned long long block_first = (unsigned long long)blockIdx.x * a.rows_per_block;
-    unsigned long long block_end = block_first + a.rows_per_block;
-    if (block_end > a.total_rows) block_end = a.total_rows;
-    unsigned long long R = block_first + wave;           // (the same for the lanes of a wave, like everything that follows from it)
-    if (R >= block_end) return;
-    long long t = (long long)(R / (unsigned long long)a.height), r = (long long)(R - (unsigned long long)t * (unsigned long long)a.height);
-    const unsigned burn = a.burn, burn4 = burn * 0x01010101u;
-    unsigned inside = 0;
-    for (; R < block_end; R += BURN_WAVES) {
-        unsigned* const row = a.acc + (unsigned long long)t * a.n_elems + (unsigned long long)(r * a.width);
-        unsigned char* const mrow = a.mask ? a.mask + (unsigned long long)t * a.mask_stride + (unsigned long long)(r * a.width) : nullptr;
-        const unsigned char* const srow = a.src ? a.src + (unsigned long long)t * a.src_stride + (unsigned long long)(r * a.width) : nullptr;
-        // slot k holds the columns 4 k - off .. 4 k - off + 3: its first pixel lies at a multiple of 16 bytes
-        const long long off = (long long)((reinterpret_cast<uintptr_t>(row) >> 2) & 3u);
-        const long long slots = (a.width + off + 3) >> 2;
-        // the four bytes of a whole slot in `mask` and `src` as one word: when they begin at a multiple of 4 bytes
-        const bool mask_words = ((reinterpret_cast<uintptr_t>(mrow) - (uintptr_t)off) & 3u) == 0u &&
-                                (!srow || ((reinterpret_cast<uintptr_t>(srow) - (uintptr_t)off) & 3u) == 0u);
-        unsigned carry = 0;                              // the XOR of the row's pixels before this step
-        for (long long s0 = 0; s0 < slots; s0 += 64) {
-            const long long c0 = 4 * (s0 + lane) - off;
-            const bool whole = c0 >= 0 && c0 + 4 <= a.width;                  // else: the head or the tail of the row, or behind it
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (whole)
-                v = *reinterpret_cast<const burn_u32x4*>(row + c0);
-            else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c0 + j >= 0 && c0 + j < a.width) v[j] = row[c0 + j];
-            }
-            v.y ^= v.x, v.z ^= v.y, v.w ^= v.z;
-            unsigned inc = v.w;                          // the inclusive prefix of the lanes' totals
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned u = __shfl_up(inc, o);
-                if (lane >= (unsigned)o) inc ^= u;
-            }
-            const unsigned before = carry ^ inc ^ v.w;
-            v.x ^= before, v.y ^= before, v.z ^= before, v.w ^= before;
-            carry ^= __shfl(inc, 63);
-            if (whole) {
-                *reinterpret_cast<burn_u32x4*>(row + c0) = v;
-                inside += (v.x != 0u) + (v.y != 0u) + (v.z != 0u) + (v.w != 0u);
-                if (mrow) {
-                    if (mask_words) {
-                        const unsigned other = srow ? *reinterpret_cast<const unsigned*>(srow + c0) : a.background * 0x01010101u;
-                        const unsigned set = (v.x ? 0xFFu : 0u) | (v.y ? 0xFF00u : 0u) | (v.z ? 0xFF0000u : 0u) | (v.w ? 0xFF000000u : 0u);
-                        *reinterpret_cast<unsigned*>(mrow + c0) = (burn4 & set) | (other & ~set);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) mrow[c0 + j] = (unsigned char)(v[j] ? burn : srow ? (unsigned)srow[c0 + j] : a.background);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (c0 + j >= 0 && c0 + j < a.width) {
-                        row[c0 + j] = v[j];
-                        inside += v[j] != 0u;
-                        if (mrow) mrow[c0 + j] = (unsigned char)(v[j] ? burn : srow ? (unsigned)srow[c0 + j] : a.background);
-                    }
-            }
-        }
-        r += BURN_WAVES;
-        while (r >= a.height) {                          // (uniform) the next row of this wave lies in another tile
-            burn_flush_inside(a, t, &inside, lane);
-            r -= a.height;
-            ++t;
-        }
-    }
-    burn_flush_inside(a, t, &inside, lane);              // (t may be n_tiles here: nothing is left to add then)
-}
+// ---- launch 2: the XOR prefix along every row, the mask, the pixels inside: dswx_ring_scan.h, which the reach shares ----------
+__global__ __launch_bounds__(BURN_BLOCK) void dswx_burn_scan_k(const BurnArgs a) { ring_scan<RingXor>(a); }
 
 }  // namespace
 

@@ -362,6 +362,12 @@ int dswx_burn_check(const void* verts, const int64_t* tile_first, const dswx_bur
 int dswx_burn_launch(dswx_ctx* ctx, const void* verts, const int64_t* tile_first, const dswx_burn_spec_t* spec, int64_t n_tiles, int64_t height,
                      int64_t width, const uint8_t* src, int64_t mask_stride, int64_t src_stride, const dswx_burn_out_t* out, hipStream_t s);
 
+// ---- reach (dswx_reach.hip): as for the burn: its checks are dswx_burn_check plus the radius and the reserved word
+int dswx_reach_check(const void* verts, const int64_t* tile_first, const dswx_reach_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,
+                     const uint8_t* src, const dswx_reach_out_t* out, int64_t* mask_stride, int64_t* src_stride, bool align);
+int dswx_reach_launch(dswx_ctx* ctx, const void* verts, const int64_t* tile_first, const dswx_reach_spec_t* spec, int64_t n_tiles, int64_t height,
+                      int64_t width, const uint8_t* src, int64_t mask_stride, int64_t src_stride, const dswx_reach_out_t* out, hipStream_t s);
+
 // ---- mosaic (dswx_mosaic.hip): the shared checks of the entries (resolves a stride of 0; `align`: the uint16 outputs must
 // be 2-byte and the placement table 4-byte aligned), and the launch for arguments that passed them
 int dswx_mosaic_check(const uint8_t* plane, const dswx_mosaic_spec_t* spec, int64_t n_tiles, int64_t height, int64_t width,

@@ -34,8 +34,12 @@ A DEM off the grid in a WGS 84 / UTM zone or in the product's own SRS is
 resampled the same way only with the keyword extension `resample_projected_dem=True`: without
 it such a file is refused as it always was (a DEM a few metres off the grid is more often a
 mistake than an intention).  Land cover in any other SRS, rotated, of several bands or not uint8, or
-across the antimeridian, a DEM in any other SRS and
-`shoreline_shapefile` raise NotImplementedError.  Pre-gridded planes can
+across the antimeridian, a DEM in any other SRS and a
+`shoreline_shapefile` that is a .shp raise NotImplementedError -- the shapefile unless the keyword extension
+`rasterise_shoreline=True` is given: then proteus_amd.shoreline reads it (geographic WGS 84 as GSHHS ships, a WGS 84 / UTM
+zone, or the product's SRS), selects and clips the polygons as _create_ocean_mask does (:3464-3572) and projects their
+vertices, and the device burns them and grows them by the margin (include/dswx_hip.h "burn", "reach": the exact buffer; the
+chords of OGR's Buffer, GEOS's Intersection and PROJ are not pinned).  Pre-gridded planes can
 also be handed over directly with the `landcover_mask=`, `shadow_layer=` and `ocean_mask=`
 keyword extensions (arrays or GeoTIFF paths).
 """
@@ -253,6 +257,8 @@ def get_dswx_hls_cli_parser():
     files('--shadow-layer', dest='shadow_layer', help='SHAD layer on the HLS grid (GeoTIFF)')
     files('--ocean-mask', dest='ocean_mask',
           help='Ocean mask on the HLS grid, 0 = ocean (GeoTIFF); needs --apply-ocean-masking')
+    p.add_argument('--rasterise-shoreline', dest='rasterise_shoreline', action='store_true', default=False,
+                   help='Take a .shp shoreline: clip and project it on the host, burn and buffer it on the GPU')
     p.add_argument('--device', dest='device', type=int, default=None, help='GPU index')
     files('--log', '--log-file', dest='log_file', help='Log file')
     p.add_argument('--full-log-format', dest='full_log_formatting', action='store_true',
@@ -343,6 +349,9 @@ def parse_runconfig_file(user_runconfig_file=None, args=None):
     for key in RunConfigConstants._FIELDS:
         if getattr(args, key, None) is None:
             setattr(args, key, getattr(consts, key))
+
+    # an extension key of this drop-in, absent from the default runconfig: the command line flag or the user's runconfig
+    args.rasterise_shoreline = bool(getattr(args, 'rasterise_shoreline', False) or processing.get('rasterise_shoreline', False))
 
     input_file_path = groups['input_file_group']['input_file_path']
     anc, paths = groups['dynamic_ancillary_file_group'], groups['product_path_group']
@@ -1293,11 +1302,13 @@ def generate_dswx_layers(input_list,
                          shadow_layer=None,
                          ocean_mask=None,
                          device=None,
-                         resample_projected_dem=False):
+                         resample_projected_dem=False,
+                         rasterise_shoreline=False):
     """Compute the DSWx-HLS layers of one HLS tile; same signature and return value as the
-    reference (:4610-4657) plus five keyword-only extensions (pre-gridded LAND / SHAD /
-    ocean planes, the GPU to use, and whether a `dem_file` off the HLS grid in a WGS 84 / UTM
-    zone or in the product's own SRS is resampled like one in EPSG:4326 instead of refused).  Returns True, or False after logging 'ERROR ...'
+    reference (:4610-4657) plus six keyword-only extensions (pre-gridded LAND / SHAD /
+    ocean planes, the GPU to use, whether a `dem_file` off the HLS grid in a WGS 84 / UTM
+    zone or in the product's own SRS is resampled like one in EPSG:4326 instead of refused, and whether a
+    `shoreline_shapefile` that is a .shp is rasterised and buffered on the device instead of refused).  Returns True, or False after logging 'ERROR ...'
     when the input cannot be read (:4988-4990)."""
     _DeferredWrites.reset()                # a previous run that raised must not leave writes deferred
     local = locals()
@@ -1369,11 +1380,19 @@ def generate_dswx_layers(input_list,
             # the shoreline polygons (0 = ocean beyond the shoreline distance, :5243-5245)
             if ocean_mask is None:
                 ocean_mask = os.fspath(shoreline_shapefile)
-        else:
+        elif not rasterise_shoreline:
             raise NotImplementedError(
                 'shoreline_shapefile: rasterising the shoreline needs GDAL/OGR, which stays on the host '
                 'and is outside this drop-in (SURVEY.md section 2); pass the ocean mask already on the '
-                'HLS grid with ocean_mask= (or give a GeoTIFF of it as shoreline_shapefile)')
+                'HLS grid with ocean_mask= (or give a GeoTIFF of it as shoreline_shapefile).  With '
+                'rasterise_shoreline=True a .shp in WGS 84 geographic or WGS 84 / UTM is clipped and projected on the '
+                'host and burnt and buffered on the device, without GDAL')
+        elif ocean_mask is None:
+            # the polygons are read, selected, clipped and projected once the grid of the product is known (below); a
+            # shapefile that cannot be taken is refused here, before anything is loaded
+            from . import shoreline as _shoreline
+            with _shoreline.read_shp(shoreline_shapefile) as shoreline_shp:
+                _shoreline.srs_of(shoreline_shp)
     if dem_file is not None and shadow_masking_algorithm == 'otsu':
         raise NotImplementedError(
             "shadow_masking_algorithm 'otsu' thresholds GDAL's hillshade (gdal.DEMProcessing, "
@@ -1470,6 +1489,16 @@ def generate_dswx_layers(input_list,
                 forest_mask_landcover_classes, dswx_metadata_dict=md, output_files_list=early_list,
                 geo_tags=geo_tags, device=device, engine=engine)
         output_landcover = None          # saved by create_landcover_mask, as in the reference
+    if ocean_mask is None and shoreline_shapefile is not None and rasterise_shoreline:
+        # :3464-3572 -- selection, clip and projection on the host; the polygons burnt and grown by the margin on the device
+        from . import shoreline as _shoreline
+        from . import warp
+        with stages.span('ocean mask (shoreline: host plan + gpu)'):
+            shore = _shoreline.plan(shoreline_shapefile, image['geotransform'], warp.epsg_of(geo_tags), length, width,
+                                    int(1000 * ocean_masking_shoreline_distance_km))
+            logger.info(f'    shoreline: {shore.polygons} polygon(s) in {shore.colours} colour(s), {shore.edges} edges '
+                        f'({shore.edges_on_clip_sides} on the clip rectangle), margin {shore.radius / 256:.2f} pixels')
+            ocean_mask = engine.shoreline_mask(shore, shape)
     landcover_mask = _as_plane(landcover_mask, shape, 'landcover_mask', engine=engine)
     shadow_layer = _as_plane(shadow_layer, shape, 'shadow_layer', engine=engine)
     ocean_mask = _as_plane(ocean_mask, shape, 'ocean_mask', engine=engine)

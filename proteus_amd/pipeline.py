@@ -343,9 +343,19 @@ class DevicePlane:
         'acc' uint32 [n, H, W] (always) and 'head' uint64 [n, 8], which stay on the device.  16 bytes per vertex cross PCIe,
         not a plane."""
         from . import burn as _burn
+        return self._rings('burn', _burn.Spec() if spec is None else spec, polygons_px, words, want)
+
+    def reach(self, polygons_px, spec, want=('acc', 'head')):
+        """The pixels of this uint8 plane whose centre lies within spec.radius (a reach.Spec, 1/256 pixel) of an edge of the
+        rings become spec.burn in place (dswx_reach_device with the plane as both `src` and `mask`;
+        proteus_amd.reach.reach_tiles with src = the same array gives the same plane); every other pixel stays.  Rings and
+        returned planes as for burn(), which it follows to give the polygons grown by the radius."""
+        return self._rings('reach', spec, polygons_px, None, want)
+
+    def _rings(self, entry, spec, polygons_px, words, want):
+        from . import burn as _burn
         if len(self.shape) not in (2, 3) or self.dtype != np.uint8:
             raise ValueError(f'polygons are burnt into a uint8 [n, H, W] or [H, W] plane, not {self.dtype} {self.shape}')
-        spec = _burn.Spec() if spec is None else spec
         if spec.mask_tile_stride or spec.src_tile_stride:
             raise ValueError('the strides of the spec must be 0: the plane is dense')
         n_tiles = self.shape[0] if len(self.shape) == 3 else 1
@@ -364,8 +374,8 @@ class DevicePlane:
         d_first = self.engine.upload(first)
         try:
             out = _capi.BurnOut.of(mask=self.ptr, **{k: p.ptr for k, p in made.items()})
-            with self.engine.lock, stages.span('gpu: burn'):
-                self.engine.ctx.burn_device(d_verts.ptr, d_first.ptr, spec, n_tiles, height, width, self.ptr, out)
+            with self.engine.lock, stages.span('gpu: ' + entry):
+                getattr(self.engine.ctx, entry + '_device')(d_verts.ptr, d_first.ptr, spec, n_tiles, height, width, self.ptr, out)
                 self.engine.ctx.synchronize()
         finally:
             d_verts.release()
@@ -825,6 +835,33 @@ class TileEngine:
             self.ctx.to_byte_device(plane.ptr, plane.dtype, plane.shape[0] * plane.shape[1], out.ptr)
             self.ctx.synchronize()
         return out
+
+    def shoreline_mask(self, plan, shape):
+        """The ocean mask of a shoreline.Plan as a resident uint8 plane of `shape`: a plane of zeros (ocean), the polygons burnt
+        as 1 (32 colours per call, in place), then every pixel within plan.radius of an edge set to 1 (dswx_burn_device,
+        dswx_reach_device).  The two record tables cross PCIe, not the plane."""
+        from . import burn as _burn
+        from . import reach as _reach
+        height, width = shape
+        mask = self.constant_plane(shape, 0)
+        acc = self.plane((1, height, width), np.uint32)
+        out = _capi.BurnOut.of(acc=acc.ptr, mask=mask.ptr)
+        tables = [(t, 'burn_device', _burn.Spec(burn=1)) for t in plan.burn_calls] + [(plan.reach, 'reach_device', _reach.Spec(plan.radius, burn=1))]
+        try:
+            for (verts, first), entry, spec in tables:
+                if not len(verts):
+                    continue
+                d_verts, d_first = self.upload(verts.view(np.uint32).reshape(-1, 4)), self.upload(first)
+                try:
+                    with self.lock, stages.span('gpu: ' + entry[:-7]):
+                        getattr(self.ctx, entry)(d_verts.ptr, d_first.ptr, spec, 1, height, width, mask.ptr, out)
+                        self.ctx.synchronize()
+                finally:
+                    d_verts.release()
+                    d_first.release()
+        finally:
+            acc.release()
+        return mask
 
     def constant_plane(self, shape, value):
         out = self.plane(shape, np.uint8)

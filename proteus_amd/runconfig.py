@@ -83,6 +83,8 @@ _PROCESSING = {
     'mask_adjacent_to_cloud_mode': s_enum('mask', 'ignore', 'cover'),
     'forest_mask_landcover_classes': s_list(_is_int),
     'ocean_masking_shoreline_distance_km': s_num(),
+    # an extension of this drop-in (not in the reference's schema): a .shp shoreline_shapefile is rasterised on the device
+    'rasterise_shoreline': s_bool,
 }
 for _l in ('wtr', 'bwtr', 'conf', 'diag', 'wtr_1', 'wtr_2', 'land', 'shad', 'cloud', 'dem',
            'rgb', 'infrared_rgb'):
